@@ -29,7 +29,6 @@ if ROOT not in sys.path:
 
 # the pool's host driver shares device memory between processes (RCCL) through dmabuf only
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")        # see pcc_amd/__init__.py: two frames in flight = four busy streams beside the default one
 import numpy as np
 import torch
 
@@ -203,6 +202,53 @@ def cpu_model_name():
     return None
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000      # --dump-outputs writes at most this much in all
+
+
+def output_arrays(last):
+    """what the caller of the timed path received from its last step, as float arrays: strings[i][j] (the bytes of each
+    stream, one value per byte), shape and k (flattened), the latent coordinates compress returned and the points decompress
+    returned, in the order they came back.  float64 for the integers (exact), float32 for bytes and decoded points."""
+    def flat(v):
+        return [x for e in v for x in flat(e)] if isinstance(v, (list, tuple)) else [int(v)]
+    out = {}
+    for i, row in enumerate(last["strings"]):
+        for j, s in enumerate(row):
+            out[f"strings_{i}_{j}"] = np.frombuffer(s, dtype=np.uint8).astype(np.float32)
+    for name in ("shape", "k"):
+        if name in last:
+            out[name] = np.asarray(flat(last[name]), dtype=np.float64)
+    if last.get("coords") is not None:
+        out["coordinates"] = last["coords"].cpu().numpy().astype(np.float64)
+    if last.get("rec") is not None:
+        out["decoded_points"] = last["rec"].cpu().numpy().astype(np.float32)
+    return out
+
+
+def fit_dump_budget(arrays, limit=DUMP_LIMIT_BYTES):
+    """keep the arrays within `limit` bytes in all: while they are over it, the largest one is replaced by a fixed, seeded
+    sample of its rows (in their original order), stored as <name>_sample beside <name>_sample_rows (the row indices)"""
+    arrays = dict(arrays)
+    while sum(a.nbytes for a in arrays.values()) > limit:
+        name = max(arrays, key=lambda n: arrays[n].nbytes)
+        a = arrays.pop(name)
+        rest = sum(b.nbytes for b in arrays.values())
+        row_bytes = a.nbytes // max(a.shape[0], 1)
+        keep = (limit - rest) // (row_bytes + 8)            # + the float64 row index
+        if keep < 1:
+            raise ValueError(f"--dump-outputs: {name} does not fit in {limit} bytes beside the other arrays")
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=int(keep), replace=False))
+        arrays[name + "_sample"] = a[rows]
+        arrays[name + "_sample_rows"] = rows.astype(np.float64)
+    return arrays
+
+
+def write_outputs(directory, arrays, suffix=""):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + suffix + ".npy"), a)
+
+
 def launch_ranks(script, argv, n_gpus):
     """`--gpus N` with N > 1 and no RANK in the environment: start the N ranks as a child process group (torchrun, one
     rank per GPU, rendezvous on 127.0.0.1) and relay rank 0's stdout; returns the exit code for this process.  The
@@ -295,7 +341,14 @@ def parse():
                     help="do not measure roofline.traffic in this run (two rocprofv3 --pmc child passes, ~40 s): replay the committed figure")
     ap.add_argument("--file-mode", action="store_true",
                     help="after the timed region, also time compress(path=...) / decompress(path=...) (t_file, SURVEY.md 8d)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (streams, shape, k, latent coordinates, "
+                         "decoded points) as DIR/<name>.npy, float32 / float64, 64 MB at most; with N > 1 every rank writes "
+                         "its own, as <name>_rank<r>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def cpu_baseline(model, state_dict, sample, dev, order="kernel"):
@@ -487,7 +540,7 @@ def main():
             t_enc += t1 - t0
             t_dec += t2 - t1b
             step_ms.append(round((t1 - t0 + t2 - t1b) * 1e3, 2))
-        last.update(strings=strings, rec=rec, k=k)
+        last.update(strings=strings, rec=rec, k=k, shape=shape, coords=coords)
 
     for _ in range(args.warmup):
         step(False)
@@ -538,6 +591,12 @@ def main():
     gc.enable()
     device_allocs_timed = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - allocs_before
     prof, sp.PROFILER = sp.PROFILER, None
+    if args.dump_outputs:
+        # now, before the records below run more steps of the same frame
+        dumped = fit_dump_budget(output_arrays(last))
+        write_outputs(args.dump_outputs, dumped, "" if world == 1 else f"_rank{rank}")
+        print(f"[bench] --dump-outputs: {', '.join(f'{n_}{list(a_.shape)}' for n_, a_ in dumped.items())} -> {args.dump_outputs}",
+              file=sys.stderr, flush=True)
 
     own_ms_per_step = elapsed / args.steps * 1e3
     rccl = rank_devices(dist, dev, world, rehearse, {"ms_per_step": round(own_ms_per_step, 3),

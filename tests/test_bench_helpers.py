@@ -109,3 +109,36 @@ def test_live_traffic_measurement_declines_inside_a_profiled_process(monkeypatch
     monkeypatch.setenv("LD_PRELOAD", "/opt/rocm/lib/librocprofiler-sdk-tool.so")
     assert bench.live_traffic("conv_mfma_buf_kernel<64, 128, 2, 2, 4, true") == "this process is itself being profiled"
     assert "--no-live-pmc" in bench.LIVE_PMC_FLAGS and "--no-cpu-baseline" in bench.LIVE_PMC_FLAGS
+
+
+def test_dump_outputs_arrays_budget_and_files(tmp_path):
+    """--dump-outputs: what compress / decompress returned, as float32 / float64 .npy files; over the byte budget the largest
+    array becomes a seeded sample of its rows, the same rows from run to run"""
+    import numpy as np
+    import torch
+    import bench
+    rec = torch.arange(60, dtype=torch.float32).reshape(10, 6) / 255.0
+    last = {"strings": [[b"\x00\x07\xff"], [b"\x10"]], "shape": [5], "k": [[7], [3], [1]],
+            "coords": torch.tensor([[0, 8, 16, 24], [0, 8, 16, 32]], dtype=torch.int32), "rec": rec}
+    a = bench.output_arrays(last)
+    assert sorted(a) == ["coordinates", "decoded_points", "k", "shape", "strings_0_0", "strings_1_0"]
+    assert a["strings_0_0"].dtype == np.float32 and a["strings_0_0"].tolist() == [0.0, 7.0, 255.0]
+    assert a["k"].dtype == np.float64 and a["k"].tolist() == [7.0, 3.0, 1.0] and a["shape"].tolist() == [5.0]
+    assert a["coordinates"].dtype == np.float64 and a["coordinates"][1].tolist() == [0.0, 8.0, 16.0, 32.0]
+    assert a["decoded_points"].dtype == np.float32 and np.array_equal(a["decoded_points"], rec.numpy())
+    assert bench.fit_dump_budget(a) == a
+    limit = sum(v.nbytes for v in a.values()) - 60
+    small = bench.fit_dump_budget(a, limit)
+    assert sum(v.nbytes for v in small.values()) <= limit and "decoded_points" not in small
+    rows = small["decoded_points_sample_rows"].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(small["decoded_points_sample"], a["decoded_points"][rows])
+    assert np.array_equal(bench.fit_dump_budget(a, limit)["decoded_points_sample_rows"], small["decoded_points_sample_rows"])
+    bench.write_outputs(str(tmp_path / "out"), a)
+    for name, v in a.items():
+        got = np.load(tmp_path / "out" / (name + ".npy"))
+        assert got.dtype == v.dtype and np.array_equal(got, v)
+
+
+def test_bench_refuses_zero_steps():
+    r = _bench(["--steps", "0"], {})
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr and not r.stdout.strip()
