@@ -10,6 +10,7 @@ import os
 import torch
 import torch.nn as nn
 
+from . import _threads
 from . import sparse as sp
 from .sparse import (ACT_NONE, ACT_RELU, ConvChain, CoordMap, MinkowskiConvolution,
                      MinkowskiGenerativeConvolutionTranspose, MinkowskiPruning, MinkowskiReLU, SparseTensor)
@@ -75,50 +76,44 @@ class ScaledBlock(nn.Module):
         return self.conv_2(h, last_residual=x.F)
 
 
-_SIDE_STREAMS = {}
-_HELPERS = {}
+def _start_prefetch(x_map, done_key, job, handoffs):
+    """What both prefetches share: unless prefetching is off (PCC_PREFETCH_MAPS=0), the path is a training one or ``x_map`` has had
+    this prefetch (``done_key``), fork the coding thread's side stream for the current stream off it and run ``job(side)`` on it —
+    on the coding thread's prefetch job thread, or in line for sets below PREFETCH_THREAD_MIN_ROWS.  What the job raises fails
+    every one of ``handoffs`` it has not set yet.  -> whether it was started.
+
+    Allocator note: everything allocated by a job belongs to the side stream's pool; a freed block can only be handed out again by a
+    later prefetch, which starts with ``side.wait_stream(main)`` — after every main-stream kernel that read the block was enqueued."""
+    if os.environ.get("PCC_PREFETCH_MAPS", "1") == "0" or torch.is_grad_enabled() or x_map._cache.get(done_key):
+        return False
+    dev = x_map.device
+    main = torch.cuda.current_stream(dev)
+    st = _threads.current()
+    skey = (dev, main.cuda_stream)            # one side stream per main stream
+    side = st.side_streams.get(skey)
+    if side is None:
+        side = st.side_streams[skey] = torch.cuda.Stream(device=dev)
+    x_map.table()              # shared with the main stream's own maps of x_map: build it there, before the fork
+    side.wait_stream(main)
+
+    def run():
+        try:
+            with torch.cuda.stream(side):
+                job(side)
+        except BaseException as e:
+            for h in handoffs:
+                h.fail(e)
+            raise
+
+    if x_map.n >= PREFETCH_THREAD_MIN_ROWS:
+        x_map._cache[("prefetch_job",)] = st.job_thread("pcc-map-prefetch", dev).submit(run)
+    else:
+        run()
+    x_map._cache[done_key] = True
+    return True
 
 
-class _PrefetchHelper:
-    """One helper thread per coding thread.  Building an up block's coordinate set reads a row count back from the device; on the
-    coding thread that read stopped the enqueueing of the main stream's own work (q_predict, ScaledBlock) for as long as the GPU
-    needed to reach it — the chip then ran dry behind every prune.  The helper makes the same calls on the side stream and does the
-    waiting; the coding thread goes on and meets it at _join_prefetch."""
-
-    def __init__(self, device):
-        import queue
-        import threading
-        self.jobs = queue.SimpleQueue()
-        self.device = device
-        self.thread = threading.Thread(target=self._run, name="pcc-map-prefetch", daemon=True)
-        self.thread.start()
-
-    def _run(self):
-        torch.cuda.set_device(self.device)          # a new thread starts on device 0
-        while True:
-            fn, done = self.jobs.get()
-            try:
-                with torch.no_grad():               # (grad mode is per thread too)
-                    fn()
-            except BaseException as e:              # re-raised on the coding thread at the join
-                done.err = e
-            done.set()
-
-    def submit(self, fn):
-        import threading
-        done = threading.Event()
-        done.err = None
-        self.jobs.put((fn, done))
-        return done
-
-
-def _helper(device):
-    import threading
-    key = (threading.get_ident(), device)
-    h = _HELPERS.get(key)
-    if h is None:
-        h = _HELPERS[key] = _PrefetchHelper(device)
-    return h
+PREFETCH_THREAD_MIN_ROWS = 8192          # below: the hand-over costs more than the wait (the 4.9 k-point frame: 5.4 -> 5.7 ms with it)
 
 
 def prefetch_up_maps(x_map):
@@ -126,53 +121,22 @@ def prefetch_up_maps(x_map):
     ``x_map`` (candidates = k3 children; parent->candidate map; candidate->candidate maps).  They are pure
     functions of the coordinates, cached on the CoordMaps, and made of hash probes and sorts — memory-
     latency work that runs beside the MFMA-bound convolutions of the same stage (q_predict, ScaledBlock)
-    instead of in front of the up block.  The calls are made by a helper thread (_PrefetchHelper), which also does the
-    waiting for the candidates' row count.  Inference path only.
+    instead of in front of the up block.  Building the candidates reads their row count back from the device; on the coding
+    thread that read stopped the enqueueing of the main stream's own work for as long as the GPU needed to reach it — the chip
+    then ran dry behind every prune.  The prefetch job thread makes the calls and does the waiting; the coding thread goes on
+    and meets it at _join_prefetch_first / _join_prefetch.  Inference path only."""
+    first = _threads.Handoff()        # the candidates and the parent -> candidate map: what the up block's first layer needs
 
-    Allocator note: everything allocated here belongs to the side stream's pool; a freed block can only be
-    handed out again by a later prefetch, which starts with ``side.wait_stream(main)`` — after every main-
-    stream kernel that read the block was enqueued."""
-    if os.environ.get("PCC_PREFETCH_MAPS", "1") == "0" or torch.is_grad_enabled():
-        return
-    key = ("okmap_prefetched",)
-    if x_map._cache.get(key):
-        return
-    dev = x_map.device
-    main = torch.cuda.current_stream(dev)
-    skey = (dev, main.cuda_stream)            # one side stream per main stream (worker threads bring their own)
-    side = _SIDE_STREAMS.get(skey)
-    if side is None:
-        side = _SIDE_STREAMS[skey] = torch.cuda.Stream(device=dev)
-    x_map.table()              # shared with the main stream's own maps of x_map: build it there, before the fork
-    side.wait_stream(main)
+    def job(side):
+        cand = x_map.up(3)
+        x_map.mfma_kernel_map(cand, 3, True)
+        first.set(side.record_event())          # the generative convolution can start; the candidates' own map follows
+        cand.mfma_kernel_map(cand, 3)
+        cand.kernel_map(cand, 3)
+        x_map._cache[("prefetch_event",)] = side.record_event()
 
-    first = _LevelSync()        # the candidates and the parent -> candidate map: what the up block's first layer needs
-
-    def job():
-        try:
-            with torch.cuda.stream(side):
-                cand = x_map.up(3)
-                x_map.mfma_kernel_map(cand, 3, True)
-                first.publish(side.record_event())          # the generative convolution can start; the candidates' own map follows
-                cand.mfma_kernel_map(cand, 3)
-                cand.kernel_map(cand, 3)
-                x_map._cache[("prefetch_event",)] = side.record_event()
-        except BaseException as e:
-            first.fail(e)
-            raise
-
-    x_map._cache[("prefetch_first",)] = first
-
-    if PREFETCH_THREAD and x_map.n >= PREFETCH_THREAD_MIN_ROWS:
-        x_map._cache[("prefetch_job",)] = _helper(dev).submit(job)
-    else:
-        job()
-    x_map._cache[key] = True
-
-
-# PCC_PREFETCH_THREAD=0: the up blocks' prefetch calls are made (and their row count waited for) on the coding thread (A/B)
-PREFETCH_THREAD = os.environ.get("PCC_PREFETCH_THREAD", "1") == "1"
-PREFETCH_THREAD_MIN_ROWS = 8192          # below: the hand-over costs more than the wait (the 4.9 k-point frame: 5.4 -> 5.7 ms with it)
+    if _start_prefetch(x_map, ("okmap_prefetched",), job, [first]):
+        x_map._cache[("prefetch_first",)] = first
 
 
 def prefetch_analysis_maps(x_map, levels=5, hyper_ups=2):
@@ -180,95 +144,54 @@ def prefetch_analysis_maps(x_map, levels=5, hyper_ups=2):
     kernel map and execution order of g_a, h_a and h_s are pure functions of the input coordinates.  Built on the side stream
     while the main stream runs the first full-resolution layers (which the caller has already enqueued), instead of one by
     one in front of the layers that use them — ~25 launches and seven count reads per frame, most of them one-workgroup
-    kernels of 30-100 us on sets the chip cannot be filled with.  The calls are made by the helper thread, which publishes every
+    kernels of 30-100 us on sets the chip cannot be filled with.  The calls are made by the job thread, which publishes every
     level as soon as its maps are in the caches; the analysis transform takes them up level by level (``join_analysis_level``).
     Inference path only."""
-    if os.environ.get("PCC_PREFETCH_MAPS", "1") == "0" or torch.is_grad_enabled():
-        return
-    key = ("analysis_prefetched",)
-    if x_map._cache.get(key):
-        return
-    dev = x_map.device
-    main = torch.cuda.current_stream(dev)
-    skey = (dev, main.cuda_stream)
-    side = _SIDE_STREAMS.get(skey)
-    if side is None:
-        side = _SIDE_STREAMS[skey] = torch.cuda.Stream(device=dev)
-    x_map.table()              # shared with the main stream's own maps of x_map: build it there, before the fork
-    side.wait_stream(main)
-    # one (host event, stream event) pair per level and one for the rest: the coding thread takes level L's maps up as soon as THEY are
-    # there (join_analysis_level) and runs that level's convolutions while the helper goes on with the coarser ones — until round 4's
-    # end the main stream stood still for ~2.4 ms at the start of every encode, waiting for all levels behind a single event
-    syncs = [_LevelSync() for _ in range(levels + 1)]
+    # one hand-over (the side stream's event) per level and one for the rest: the coding thread takes level L's maps up as soon as
+    # THEY are there (join_analysis_level) and runs that level's convolutions while the job thread goes on with the coarser ones —
+    # until round 4's end the main stream stood still for ~2.4 ms at the start of every encode, waiting for all levels behind a
+    # single event
+    syncs = [_threads.Handoff() for _ in range(levels + 1)]
 
-    def job():
-        try:
-            with torch.cuda.stream(side):
-                m, sets = x_map, [x_map]
-                for lv in range(levels):
-                    d = m.down()
-                    m.mfma_kernel_map(d, 3)                          # the stride-2 convolution onto the coarser set
-                    d.mfma_kernel_map(d, 3)                          # the stride-1 convolutions on it
-                    sets.append(d)
-                    m = d
-                    syncs[lv].publish(side.record_event())
-                y_map = sets[3] if len(sets) > 3 else None           # stride 8: the latents' set; h_s ends on it
-                u = m
-                for _ in range(hyper_ups if y_map is not None and levels >= 5 else 0):
-                    c = u.up(2)                                      # h_s: generative transposed convolutions, kernel 2
-                    u.mfma_kernel_map(c, 2, True)
-                    c.mfma_kernel_map(c, 3)
-                    u = c
-                if y_map is not None and u is not m:
-                    u.mfma_kernel_map(y_map, 3)                      # h_s's last layer, evaluated at the latents' coordinates
-                syncs[levels].publish(side.record_event())
-        except BaseException as e:
-            for sy in syncs:
-                sy.fail(e)
-            raise
+    def job(side):
+        m, sets = x_map, [x_map]
+        for lv in range(levels):
+            d = m.down()
+            m.mfma_kernel_map(d, 3)                          # the stride-2 convolution onto the coarser set
+            d.mfma_kernel_map(d, 3)                          # the stride-1 convolutions on it
+            sets.append(d)
+            m = d
+            syncs[lv].set(side.record_event())
+        y_map = sets[3] if len(sets) > 3 else None           # stride 8: the latents' set; h_s ends on it
+        u = m
+        for _ in range(hyper_ups if y_map is not None and levels >= 5 else 0):
+            c = u.up(2)                                      # h_s: generative transposed convolutions, kernel 2
+            u.mfma_kernel_map(c, 2, True)
+            c.mfma_kernel_map(c, 3)
+            u = c
+        if y_map is not None and u is not m:
+            u.mfma_kernel_map(y_map, 3)                      # h_s's last layer, evaluated at the latents' coordinates
+        syncs[levels].set(side.record_event())
 
-    x_map._cache[("analysis_syncs",)] = syncs
-    if PREFETCH_THREAD and x_map.n >= PREFETCH_THREAD_MIN_ROWS:
-        x_map._cache[("prefetch_job",)] = _helper(dev).submit(job)
-    else:
-        job()
-    x_map._cache[key] = True
-
-
-class _LevelSync:
-    """what one level of prefetch_analysis_maps hands over: set once its maps are in the caches, with the side stream's event behind them"""
-
-    def __init__(self):
-        import threading
-        self.ready = threading.Event()
-        self.event = None
-        self.err = None
-
-    def publish(self, event):
-        self.event = event
-        self.ready.set()
-
-    def fail(self, err):
-        if not self.ready.is_set():
-            self.err = err
-            self.ready.set()
+    if _start_prefetch(x_map, ("analysis_prefetched",), job, syncs):
+        x_map._cache[("analysis_syncs",)] = syncs
 
 
 def join_analysis_level(x_map, level):
     """Before the coding thread touches the coordinate set / maps of stride 2^level below ``x_map`` (level 1 = the first stride-2 set;
-    level = -1: everything, incl. the hyper-latents' sets): wait for the helper to have put them into the caches, and make the current
-    stream wait for the side stream's kernels behind them.  No-op when nothing was prefetched."""
+    level = -1: everything, incl. the hyper-latents' sets): wait for the job thread to have put them into the caches, and make the
+    current stream wait for the side stream's kernels behind them.  No-op when nothing was prefetched."""
     syncs = x_map._cache.get(("analysis_syncs",))
     if not syncs:
         return
     last = level == -1 or level >= len(syncs)
-    sy = syncs[-1] if last else syncs[level - 1]
-    sy.ready.wait()
-    if sy.err is not None:
+    try:
+        ev = (syncs[-1] if last else syncs[level - 1]).wait()
+    except BaseException:
         x_map._cache.pop(("analysis_syncs",), None)
         x_map._cache.pop(("prefetch_job",), None)
-        raise sy.err
-    torch.cuda.current_stream(x_map.device).wait_event(sy.event)
+        raise
+    torch.cuda.current_stream(x_map.device).wait_event(ev)
     if last:
         x_map._cache.pop(("analysis_syncs",), None)
         _join_prefetch(x_map)
@@ -276,14 +199,15 @@ def join_analysis_level(x_map, level):
 
 def _join_prefetch_first(x_map):
     """the first publication of prefetch_up_maps (candidates + parent -> candidate map): the rest is joined by _join_prefetch"""
-    sy = x_map._cache.pop(("prefetch_first",), None)
-    if sy is None:
+    first = x_map._cache.pop(("prefetch_first",), None)
+    if first is None:
         return
-    sy.ready.wait()
-    if sy.err is not None:
+    try:
+        ev = first.wait()
+    except BaseException:
         x_map._cache.pop(("prefetch_job",), None)
-        raise sy.err
-    torch.cuda.current_stream(x_map.device).wait_event(sy.event)
+        raise
+    torch.cuda.current_stream(x_map.device).wait_event(ev)
 
 
 def _join_prefetch(x_map):
@@ -291,8 +215,6 @@ def _join_prefetch(x_map):
     done = x_map._cache.pop(("prefetch_job",), None)
     if done is not None:
         done.wait()
-        if done.err is not None:
-            raise done.err
     ev = x_map._cache.pop(("prefetch_event",), None)
     if ev is not None:
         torch.cuda.current_stream(x_map.device).wait_event(ev)

@@ -9,16 +9,15 @@ host at ``update()`` (one-off) and the rANS coder is the host C++ one in the sam
 (SURVEY.md N12-N14).  Training mode — additive U(-.5, .5) noise instead of rounding, likelihoods differentiable through torch
 ops, compressai's LowerBound gradients — is ``forward(..., training=True)`` / ``module.train()``.
 """
+import functools
 import math
-
-import threading
 
 import numpy as np
 import scipy.stats
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, _threads
 from ._lib import check, ptr
 
 SCALES_MIN, SCALES_MAX, SCALES_LEVELS = 0.11, 256.0, 64
@@ -82,23 +81,17 @@ def _pmf_to_cdf(pmf, tail, pmf_length, max_length):
     return cdf
 
 
-# Pinned staging buffers for the symbol / index planes (the only per-frame host traffic of the
-# path): page-locked copies run at PCIe rate instead of through a pageable bounce buffer.
-_PINNED = {}
-
-
-_PIN_BUSY = {}      # (thread, key) -> event recorded behind the last asynchronous upload FROM that staging buffer
-
-
 def _pinned(key, numel, dtype):
-    key = (threading.get_ident(), key)         # one staging set per worker thread (streamed sequences: one thread per frame in flight)
-    ev = _PIN_BUSY.pop(key, None)
+    """The calling thread's pinned staging buffer ``key`` for the symbol / index planes (the only per-frame host traffic of the
+    path): page-locked copies run at PCIe rate instead of through a pageable bounce buffer.  One staging set per coding thread
+    (streamed sequences: one thread per frame in flight)."""
+    st = _threads.current()
+    ev = st.pin_busy.pop(key, None)
     if ev is not None:
         ev.synchronize()                       # the previous upload from this buffer (long done by now) before it is rewritten
-    buf = _PINNED.get(key)
+    buf = st.pinned.get(key)
     if buf is None or buf.numel() < numel or buf.dtype != dtype:
-        buf = torch.empty(max(numel, 1), dtype=dtype, pin_memory=True)
-        _PINNED[key] = buf
+        buf = st.pinned[key] = torch.empty(max(numel, 1), dtype=dtype, pin_memory=True)
     return buf[:numel]
 
 
@@ -127,7 +120,7 @@ def _upload_guard(key, device):
     (the kernel maps in front of h_s, the prefetched maps in front of g_s) and the chip then idled while the thread caught up"""
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(device))
-    _PIN_BUSY[(threading.get_ident(), key)] = ev
+    _threads.current().pin_busy[key] = ev
 
 
 def _to_device(arr, device, key):
@@ -140,62 +133,18 @@ def _to_device(arr, device, key):
     return out
 
 
-class _HostWorker:
-    """A persistent thread per coding thread for the serial range-coder calls that run beside GPU work (the C calls release the
-    interpreter lock).  Creating a thread per call cost the coding thread ~0.3 ms at the start of every decode (thread start + the new
+def _rans_thread():
+    """The coding thread's job thread for the serial range-coder calls that run beside GPU work (the C calls release the interpreter
+    lock).  Persistent: creating a thread per call cost the coding thread ~0.3 ms at the start of every decode (thread start + the new
     thread's Python prelude under the lock) — on the critical path, with the GPU idle."""
-
-    def __init__(self):
-        import queue
-        self.jobs = queue.SimpleQueue()
-        self.thread = threading.Thread(target=self._run, name="pcc-rans", daemon=True)
-        self.thread.start()
-
-    def _run(self):
-        while True:
-            fn, done = self.jobs.get()
-            try:
-                fn()
-            except BaseException as e:      # re-raised on the coding thread by wait()
-                done.err = e
-            done.set()
-
-    def submit(self, fn):
-        done = threading.Event()
-        done.err = None
-        self.jobs.put((fn, done))
-        return done
+    return _threads.current().job_thread("pcc-rans")
 
 
-_WORKERS = {}
-
-
-def _host_worker():
-    key = threading.get_ident()
-    w = _WORKERS.get(key)
-    if w is None:
-        w = _WORKERS[key] = _HostWorker()
-    return w
-
-
-def _wait(done):
-    done.wait()
-    if done.err is not None:
-        raise done.err
-
-
-_CHANNEL_INDEX_PLANES = {}
-
-
+@functools.lru_cache(maxsize=64)
 def _channel_index_plane(c, n):
-    """np.repeat(np.arange(c), n) as int32 (the factorized model's indexes: channel-major planes), cached: 150 k elements per decode"""
-    key = (c, n)
-    hit = _CHANNEL_INDEX_PLANES.get(key)
-    if hit is None:
-        if len(_CHANNEL_INDEX_PLANES) > 64:
-            _CHANNEL_INDEX_PLANES.clear()
-        hit = _CHANNEL_INDEX_PLANES[key] = np.repeat(np.arange(c, dtype=np.int32), n)
-    return hit
+    """np.repeat(np.arange(c), n) as int32 (the factorized model's indexes: channel-major planes), cached: 150 k elements per decode.
+    An eviction drops the cache's reference only: a decode in flight holds its own."""
+    return np.repeat(np.arange(c, dtype=np.int32), n)
 
 
 def _rans_encode(symbols, indexes, cdf, cdf_length, offset):
@@ -463,7 +412,6 @@ class EntropyBottleneck(_EntropyModelBase):
         depend on coordinates only."""
         cdf, cdf_len, off = self.tables()
         c = self.channels
-        box = {}
         indexes = _channel_index_plane(c, n)
         # everything the call needs is prepared HERE: the worker's job is the C call alone (it releases the interpreter lock; Python
         # steps on the worker would each queue for the lock this thread holds while it builds the kernel maps)
@@ -473,14 +421,13 @@ class EntropyBottleneck(_EntropyModelBase):
         fn = _lib.lib().pcc_rans_decode_with_indexes
         args = (ptr(buf), len(strings[0]), ptr(indexes), indexes.size, ptr(cdf), cdf.shape[1], ptr(cdf_len), ptr(off), ptr(out))
 
-        def work():
-            box["rc"] = fn(*args)
+        def work(_held=(buf, indexes, cdf, cdf_len, off, out)):      # the arrays behind the addresses live as long as the job
+            return fn(*args)
 
-        done = _host_worker().submit(work)
+        done = _rans_thread().submit(work)
 
         def finish():
-            _wait(done)
-            check(box["rc"])
+            check(done.wait())
             sym = sym_host.to(device, non_blocking=True).reshape(c, n)
             _upload_guard("eb_sym32", device)
             zhat = torch.empty((n, c), dtype=torch.float32, device=device)
@@ -601,7 +548,6 @@ class GaussianConditional(_EntropyModelBase):
         decode runs on a worker thread (the C call releases the GIL).  Returns a function that joins the
         thread, uploads the symbols and returns y_hat [N, C]; in between the caller can enqueue GPU
         work that does not depend on y (h_q, kernel maps of the first synthesis stage)."""
-        import threading
         n = params.shape[0]
         dev = params.device
         cn = c * n
@@ -612,7 +558,6 @@ class GaussianConditional(_EntropyModelBase):
         idx_host, idx_ev = _to_host_async(idx_dev, "gc_idx8")      # the worker waits for the copy; this thread goes on enqueueing h_q
         sym_host = _pinned("gc_sym16", cn, torch.int16)
         cdf, cdf_len, off = self.tables()
-        box = {}
 
         # (arguments prepared here, the worker's job is the event wait and the C call: see the factorized model's decode)
         buf = np.frombuffer(strings[0], dtype=np.uint8)
@@ -621,26 +566,24 @@ class GaussianConditional(_EntropyModelBase):
         fn = _lib.lib().pcc_rans_decode_with_indexes_u8i16
         args = (ptr(buf), len(strings[0]), ptr(idx_host), idx_host.size, ptr(cdf), cdf.shape[1], ptr(cdf_len), ptr(off), ptr(sym_np), ptr(narrowed))
 
-        def work():
+        def work(_held=(buf, idx_host, cdf, cdf_len, off, sym_np, narrowed)):     # (as in the factorized model's decode)
             idx_ev.synchronize()
             check(fn(*args))
-            box["fits"] = int(narrowed[0]) == 0
-            if not box["fits"]:                                              # a symbol beyond int16: int32 planes
-                box["sym"] = _rans_decode(strings[0], idx_host.astype(np.int32), cdf, cdf_len, off)
+            if int(narrowed[0]) == 0:
+                return None
+            return _rans_decode(strings[0], idx_host.astype(np.int32), cdf, cdf_len, off)      # a symbol beyond int16: int32 planes
 
-        done = _host_worker().submit(work)
+        done = _rans_thread().submit(work)
 
         def finish():
-            _wait(done)
-            if "err" in box:
-                raise box["err"]
+            wide = done.wait()
             yhat = torch.empty((n, c), dtype=torch.float32, device=dev)
-            if box["fits"]:
+            if wide is None:
                 sym = sym_host.to(dev, non_blocking=True)
                 _upload_guard("gc_sym16", dev)                                   # the pinned plane is reused by the next frame
                 check(_lib.lib().pcc_gc_dequantize_i16(ptr(sym), ptr(params.contiguous()), n, c, ptr(yhat), _lib.stream()))
             else:
-                sym = _to_device(box["sym"].reshape(c, n), dev, "gc_sym_up")
+                sym = _to_device(wide.reshape(c, n), dev, "gc_sym_up")
                 check(_lib.lib().pcc_gc_dequantize(ptr(sym), ptr(params.contiguous()), n, c, ptr(yhat), _lib.stream()))
             return yhat
 

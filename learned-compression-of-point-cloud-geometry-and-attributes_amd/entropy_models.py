@@ -202,8 +202,9 @@ class MeanScaleHyperprior_Map(nn.Module):
         y_strings = finish_y()
         return points, [y_strings, z_strings], shape
 
-    def decompress(self, points, strings, shape):
-        """entropy_models.py:384-414 -> (y_hat, Q_hat); ``points`` = [coords8, coords32] or CoordMaps."""
+    def decompress(self, points, strings, shape, finish_z=None):
+        """entropy_models.py:384-414 -> (y_hat, Q_hat); ``points`` = [coords8, coords32] or CoordMaps.  ``finish_z``: what
+        start_z_decode returned for these strings, when the caller started the z decode earlier."""
         assert isinstance(strings, list) and len(strings) == 2
         y_map, z_map = points
         if not isinstance(y_map, CoordMap):
@@ -216,10 +217,7 @@ class MeanScaleHyperprior_Map(nn.Module):
         y_strings, z_strings = strings
         # the z stream needs nothing from the GPU: its host decode runs while the GPU builds what depends on coordinates
         # only — the tables and kernel maps of h_s (z -> 16 -> 8, evaluated at y) and of the first h_q layer
-        early = self.__dict__.pop("_early_z", None)                   # ColorModel.decompress starts it before the coordinate sets
-        if early is not None and early[0] is strings:                 # (a decode started for THESE strings: an earlier call may have failed)
-            finish_z = early[1]
-        else:
+        if finish_z is None:                                          # (ColorModel.decompress starts it before the coordinate sets)
             finish_z = self.entropy_bottleneck.decompress_features_async(z_strings, int(shape[0]), z_sorted.device)
         z_sorted.mfma_kernel_map(z_sorted, 3)
         z16 = z_sorted.up(2)
@@ -240,8 +238,8 @@ class MeanScaleHyperprior_Map(nn.Module):
 
     def start_z_decode(self, strings, shape, device):
         """The z stream needs nothing but its bytes: its host decode (0.6-0.8 ms on the config-2 frame) can start before the first
-        coordinate set of a decompress is built; decompress() picks the pending result up."""
-        self.__dict__["_early_z"] = (strings, self.entropy_bottleneck.decompress_features_async(strings[1], int(shape[0]), device))
+        coordinate set of a decompress is built.  -> the function that finishes it: decompress(..., finish_z=) takes it."""
+        return self.entropy_bottleneck.decompress_features_async(strings[1], int(shape[0]), device)
 
     @staticmethod
     def _prefetch_synthesis_maps(y_map, q_map):

@@ -132,11 +132,11 @@ class ColorModel(nn.Module):
             coordinates = torch.cat([batch, coordinates], dim=1)
         nbatch = len(k[0]) if isinstance(k[0], (list, tuple)) else 1          # one count per item and stage
         if self.entropy_model_map is None:
-            self.entropy_model.start_z_decode(strings, shape, device)           # host work that needs no coordinates: first
+            finish_z = self.entropy_model.start_z_decode(strings, shape, device)          # host work that needs no coordinates: first
         c8 = CoordMap(sp._as_int_coords(coordinates.to(device)), 8, nbatch=nbatch)
         c32 = c8.down().down()      # coordinates only (g_s.down_conv applied twice, model.py:188-190)
         if self.entropy_model_map is None:
-            y_hat, Q_hat = self.entropy_model.decompress([c8, c32], strings, shape)
+            y_hat, Q_hat = self.entropy_model.decompress([c8, c32], strings, shape, finish_z=finish_z)
         else:
             points = [_canonical_map(c8, 8), _canonical_map(c32, 32)]          # model/model.py:197-201: both models decode on the same lists
             y_hat = self.entropy_model.decompress(points, strings[0], shape[0])

@@ -18,7 +18,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, _threads
 from ._lib import check, ptr
 
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
@@ -61,22 +61,17 @@ def _as_int_coords(coords):
     return coords.to(torch.int32).contiguous()
 
 
-_COUNT_BUFS = {}
-
-
 def _host_count():
     """A page-locked int64 the device writes a row count into directly (zero-copy).  The count kernel (the scan of the
     block sums) runs BEFORE the kernels that move the rows, so the host — which polls the word instead of synchronising
     the stream — learns the count while those are still running and goes on allocating and enqueueing.  One word per
-    host thread (worker threads code frames concurrently); armed with -1 before every use."""
-    import threading
-    key = threading.get_ident()
-    hit = _COUNT_BUFS.get(key)
-    if hit is None:
+    host thread (worker threads code frames concurrently); armed with -1 before every use.  -> (tensor, numpy view)"""
+    st = _threads.current()
+    if st.count is None:
         buf = torch.zeros(1, dtype=torch.int64, pin_memory=True)
-        hit = _COUNT_BUFS[key] = (buf, buf.numpy())
-    hit[1][0] = -1
-    return hit[0]
+        st.count = (buf, buf.numpy())
+    st.count[1][0] = COUNT_ARMED
+    return st.count
 
 
 _SMALL_MAP_MAX = None
@@ -109,24 +104,21 @@ class CoordinateRangeError(ValueError):
 
 
 COUNT_ARMED, COUNT_ERR_RANGE = -1, -2            # PCC_COUNT_ERR_RANGE of include/pcc_hip.h
-_POLL_YIELD = os.environ.get("PCC_COUNT_POLL_YIELD", "1") == "1"      # 0: spin without yielding the interpreter lock (A/B)
 
 
-def _read_count(buf, device):
-    """The row count the scan kernel wrote into this thread's page-locked word.  A short poll (the kernel that writes it
-    runs ahead of the row movers, so the word usually lands while the host is still here), yielding the interpreter lock
-    between reads so that the other coding threads of a streamed run are not starved; then a real wait on the stream,
+def _read_count(word, device):
+    """The row count the scan kernel wrote into ``word`` (the numpy view of _host_count()).  A short poll (the kernel that
+    writes it runs ahead of the row movers, so the word usually lands while the host is still here), yielding the interpreter
+    lock between reads so that the other coding threads of a streamed run are not starved; then a real wait on the stream,
     which releases the lock for its whole duration."""
     import time
-    arr = _COUNT_BUFS[__import__("threading").get_ident()][1]
     deadline = time.perf_counter() + 2e-3
-    while arr[0] == COUNT_ARMED:
+    while word[0] == COUNT_ARMED:
         if time.perf_counter() > deadline:        # not visible yet (or the stream is behind): fall back to a real wait
             torch.cuda.current_stream(device).synchronize()
             break
-        if _POLL_YIELD:
-            time.sleep(0)
-    n = int(arr[0])
+        time.sleep(0)
+    n = int(word[0])
     if n == COUNT_ERR_RANGE:
         raise CoordinateRangeError("libpcc_hip: a voxel coordinate is outside the supported range (|c| <= 130000, batch index "
                                    "<= 1022): the 18-bit fields of the voxel key would alias — translate the cloud towards the "
@@ -240,11 +232,11 @@ class CoordMap:
         vals = torch.empty(cap, dtype=torch.int32, device=dev)
         scratch = torch.empty(L.pcc_scan_scratch_elems(m), dtype=torch.int32, device=dev)
         out = torch.empty((max(m, 1), 4), dtype=torch.int32, device=dev)
-        count = _host_count()
+        count, word = _host_count()
         ev = _cp_begin()
         check(getattr(L, fn_name)(ptr(self.coords), self.n, *args, ptr(keys), ptr(vals), cap, ptr(scratch),
                                   ptr(out), ptr(count), _lib.stream()))
-        n_out = _read_count(count, dev)      # the one host sync of a coordinate-set construction
+        n_out = _read_count(word, dev)      # the one host sync of a coordinate-set construction
         # table cleared, 16 B per source row, 12 B per candidate (key claim + flag), 16 B + 12 B per unique row written
         _cp_end(ev, "unique_" + fn_name[4:], m, 12 * cap + 16 * self.n + 12 * m + 28 * n_out)
         return out[:n_out], (keys, vals, cap)
@@ -544,7 +536,7 @@ def compact_rows(mask, coords=None, feats=None, want_index=False, expected=None)
     dev = mask.device
     scratch = torch.empty(L.pcc_scan_scratch_elems(n), dtype=torch.int32, device=dev)
     known = expected is not None and n > 0 and not CHECK_EXPECTED_COUNTS
-    count = None if known else _host_count()
+    count, word = (None, None) if known else _host_count()
     out_c = torch.empty((n, 4), dtype=torch.int32, device=dev) if coords is not None else None
     c = feats.shape[1] if feats is not None else 0
     out_f = torch.empty((n, c), dtype=torch.float32, device=dev) if feats is not None else None
@@ -555,7 +547,7 @@ def compact_rows(mask, coords=None, feats=None, want_index=False, expected=None)
     if known:
         m = int(expected)
     else:
-        m = _read_count(count, dev)
+        m = _read_count(word, dev)
         if expected is not None and m != int(expected):
             raise RuntimeError(f"compact_rows: {m} rows kept where the caller expected {int(expected)}")
     # mask + scan per row, coordinates and features of the kept rows read and written

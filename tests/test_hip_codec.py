@@ -340,14 +340,14 @@ def test_translated_clouds_code_to_the_same_bytes_up_to_the_reference_key_range(
         assert np.array_equal(a[:, :3], b[:, :3] + off) and np.array_equal(a[:, 3:], b[:, 3:]), off
 
 
-def test_an_error_inside_the_prefetch_helper_thread_reaches_the_caller(pcc, model, monkeypatch):
-    """the up blocks' coordinate sets are generated by a helper thread (blocks._PrefetchHelper): whatever is raised there must surface
-    at the join on the coding thread, and the helper must go on serving jobs.  (A range error cannot be provoked through the codec
-    itself: wherever the encoder's coordinate sets fit the key range the decoder's do too.)"""
-    from pcc_amd import blocks
+def test_an_error_inside_the_prefetch_job_thread_reaches_the_caller(pcc, model, monkeypatch):
+    """the up blocks' coordinate sets are generated by the coding thread's prefetch job thread (pcc_amd._threads): whatever is raised
+    there must surface at the join on the coding thread, and the job thread must go on serving jobs.  (A range error cannot be
+    provoked through the codec itself: wherever the encoder's coordinate sets fit the key range the decoder's do too.)"""
+    from pcc_amd import _threads, blocks
     dev = torch.device(DEV)
     m = pcc.CoordMap(torch.tensor([[0, 8, 8, 8], [0, 16, 8, 8]], dtype=torch.int32, device=dev), 8, nbatch=1)
-    helper = blocks._helper(dev)
+    helper = _threads.current().job_thread("pcc-map-prefetch", dev)
     def failing_job():
         m.table()                                                              # (real work on the side thread first)
         raise pcc.sparse.CoordinateRangeError("raised on the helper thread")
@@ -357,14 +357,15 @@ def test_an_error_inside_the_prefetch_helper_thread_reaches_the_caller(pcc, mode
     assert ("prefetch_job",) not in m._cache
     done = helper.submit(lambda: m.up(3))                                     # the same thread serves the next job
     done.wait()
-    assert done.err is None and m.up(3).n == 2 * 27 - 9
+    assert m.up(3).n == 2 * 27 - 9
+    assert _threads.current().job_thread("pcc-map-prefetch", dev) is helper
     # and through the codec, with the helper forced on for a tiny cloud: same bytes, same reconstruction as in line
     monkeypatch.setattr(blocks, "PREFETCH_THREAD_MIN_ROWS", 0)
     pts = pcc.synthetic.sphere_shell(**pcc.synthetic.CONFIG1)
     qc, qf = pcc.synthetic.uniform_qmap(pts[:, :3], 0.5, 0.5)
     strings, shape, k, coords = _compress(pcc, model, pts, qc, qf)
     rec_t = model.decompress(coordinates=coords, strings=strings, shape=shape, k=k).cpu().numpy()
-    monkeypatch.setattr(blocks, "PREFETCH_THREAD", False)
+    monkeypatch.setattr(blocks, "PREFETCH_THREAD_MIN_ROWS", 1 << 62)         # in line
     rec_i = model.decompress(coordinates=coords, strings=strings, shape=shape, k=k).cpu().numpy()
     assert np.array_equal(rec_t, rec_i)
 
@@ -443,6 +444,7 @@ def test_two_worker_threads_produce_identical_frames(pcc):
     every frame must come out bit-identical to the single-threaded result"""
     import hashlib
     import threading
+    import time
     syn = pcc.synthetic
     model = syn.make_model(0, "cuda:0")
     model.update()
@@ -463,6 +465,8 @@ def test_two_worker_threads_produce_identical_frames(pcc):
 
     want = [code(i) for i in range(3)]
     got, errs, lock, nxt = {}, [], threading.Lock(), [0]
+    helpers = ("pcc-map-prefetch", "pcc-rans")
+    before = {t for t in threading.enumerate() if t.name in helpers}              # (the main thread's own)
 
     def worker():
         try:
@@ -484,6 +488,11 @@ def test_two_worker_threads_produce_identical_frames(pcc):
     [t.join() for t in ths]
     assert not errs, errs
     assert [got[i] for i in range(12)] == [want[i % 3] for i in range(12)]
+    # the job threads the two coding threads started end with them
+    deadline = time.monotonic() + 5.0
+    while {t for t in threading.enumerate() if t.name in helpers} - before and time.monotonic() < deadline:
+        time.sleep(0.01)
+    assert not {t for t in threading.enumerate() if t.name in helpers} - before
 
 
 @pytest.mark.gpu

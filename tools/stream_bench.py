@@ -5,7 +5,7 @@ worker waits for its serial host range coder (16-17 ms per frame, GIL released) 
 Not the headline metric: bench.py times one frame at a time.
 
   python tools/stream_bench.py [--frames 12] [--workers 2]"""
-import argparse, json, os, sys, threading, time
+import argparse, json, os, queue, sys, threading, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch
@@ -32,26 +32,41 @@ def code(i):
     rec = model.decompress(coordinates=coords, strings=strings, shape=shape, k=k)
     return rec.shape[0], pcc_amd.utils.count_bits(strings)
 
-def run(workers, n_frames):
-    nxt, lock, done = [0], threading.Lock(), []
+def start_workers(workers):
+    """W persistent workers (bench.py's `streamed` record has the same shape): a coding thread owns its pinned staging, count
+    word, side streams and job threads for as long as it lives, so the warm-up run must be made by the threads that are timed"""
+    jobs, results = queue.SimpleQueue(), queue.SimpleQueue()
     def worker():
         s = torch.cuda.Stream(device=dev)
         with torch.cuda.stream(s):
-            while True:
-                with lock:
-                    i = nxt[0]; nxt[0] += 1
-                if i >= n_frames:
-                    break
-                done.append(code(i))
-            s.synchronize()
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    ths = [threading.Thread(target=worker) for _ in range(workers)]
-    for wi, t in enumerate(ths):
-        if wi:
-            time.sleep(STAGGER_S)                      # frames arrive one after the other (bench.py: lock-step otherwise)
-        t.start()
+            while (i := jobs.get()) is not None:
+                if isinstance(i, tuple):               # ("hold", k): frames arrive one after the other (bench.py: lock-step otherwise)
+                    time.sleep(i[1] * STAGGER_S)
+                    continue
+                try:
+                    results.put(code(i))
+                except BaseException as e:             # surfaced by run()
+                    results.put(e)
+    ths = [threading.Thread(target=worker, daemon=True) for _ in range(workers)]
+    [t.start() for t in ths]
+    return ths, jobs, results
+
+def stop_workers(pool):
+    ths, jobs, _ = pool
+    [jobs.put(None) for _ in ths]
     [t.join() for t in ths]
+
+def run(pool, n_frames):
+    ths, jobs, results = pool
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    jobs.put(0)                                       # the first worker starts at once, the k-th further one k holds later
+    [jobs.put(("hold", k)) for k in range(1, len(ths))]
+    [jobs.put(i) for i in range(1, n_frames)]
+    done = [results.get() for _ in range(n_frames)]
     torch.cuda.synchronize()
+    for d in done:
+        if isinstance(d, BaseException):
+            raise d
     return time.perf_counter() - t0, done
 
 STAGGER_S = 0.0
@@ -60,8 +75,10 @@ torch.cuda.synchronize(); _t = time.perf_counter(); code(0); torch.cuda.synchron
 STAGGER_S = 0.5 * (time.perf_counter() - _t)          # half a sequential frame
 out = {}
 for w in sorted({1, args.workers}):
-    run(w, w * 2)                                     # per-thread warm-up (pinned staging, side streams)
-    el, done = run(w, args.frames)
+    pool = start_workers(w)
+    run(pool, w * 2)                                  # per-thread warm-up (pinned staging, side streams)
+    el, done = run(pool, args.frames)
+    stop_workers(pool)
     pts_total = sum(d[0] for d in done)
     out[f"workers_{w}"] = {"frames": args.frames, "seconds": el, "ms_per_frame": 1e3 * el / args.frames, "mpoints_per_s": pts_total / el / 1e6}
     print(w, "workers:", out[f"workers_{w}"], flush=True)
