@@ -183,6 +183,13 @@ int pcc_conv_fwd(const float* fin, int64_t n_in, int32_t cin, const float* w, co
  * 640, or PCC_CONV_SMALL_MAX; 0 = never) and returns the previous one; a negative argument only reads it. */
 int64_t pcc_conv_small_max(int64_t workgroups);
 
+/* The kernel a forward launch of `mode` (0 = pcc_conv_fwd, 1 = pcc_conv_fwd_bf16, 2 = pcc_conv_fwd_x3) runs on this shape,
+ * spelled as the profiler prints it (bf16 / x3 names carry a "[bf16]" / "[x3]" tag after the kernel's name), written to
+ * `buf` (`len` bytes; buf == NULL only asks whether the mode runs the shape).  Host only, launches nothing.
+ * PCC_ERR_UNSUPPORTED when that mode cannot run the shape. */
+int pcc_conv_kernel_name(int32_t mode, int64_t n_in, int32_t cin, int32_t cout, int64_t n_out, int32_t K, int32_t has_nbr,
+                         char* buf, int32_t len);
+
 /* bf16-input variant of pcc_conv_fwd (training / BASELINE config 5): features and packed weights are bf16
  * (fin [n_in, cin] bf16, cin a multiple of 64; pcc_conv_pack_weights_bf16: [K, cin/8, cout^32, 8]), products
  * accumulate in fp32 on v_mfma_f32_32x32x16_bf16, bias / FiLM / activation / residual and the output are fp32.

@@ -37,6 +37,7 @@ SIGNATURES = {
     "pcc_conv_fwd": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
                              c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
     "pcc_conv_small_max": (c_i64, [c_i64]),
+    "pcc_conv_kernel_name": (c_int, [c_i32, c_i64, c_i32, c_i32, c_i64, c_i32, c_i32, ctypes.c_char_p, c_i32]),
     "pcc_small_map_max": (c_i64, []),
     "pcc_small_paths": (c_i32, [c_i32]),
     "pcc_small_kernel_map": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p,

@@ -17,6 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
+from .sparse import MODE_BF16, MODE_F32, MODE_X3, launch_mode, pack_weights
 
 _THIN_CIN = (1, 2, 3, 4, 6, 8, 12, 16, 24)
 
@@ -44,46 +45,29 @@ def set_x3(enabled):
     X3 = bool(enabled)
 
 
-def _x3_ok(rows, cin, cout, n_out, K, has_nbr):
-    return (X3 and cin % 32 == 0 and ((cout + 31) // 32 * 32) % 64 == 0 and rows * cin * 4 < 0xFFFFF000
-            and (not has_nbr or n_out * K * 4 < 0xFFFFF000))
-
-
-def _packed(w):
-    """[K, cin, cout] -> MFMA packing (or None for thin cin)"""
-    K, cin, cout = w.shape
-    if cin % 32:
-        return None
-    L = _lib.lib()
-    wp = torch.empty(L.pcc_conv_packed_elems(K, cin, cout), dtype=torch.float32, device=w.device)
-    check(L.pcc_conv_pack_weights(ptr(w), K, cin, cout, ptr(wp), _lib.stream()))
-    return wp
-
-
-def _bf16_ok(rows, cin):
-    return BF16 and cin % 64 == 0 and rows * cin * 2 < 0xFFFFF000
+def _mode(rows, cin, cout, n_out, K, has_nbr):
+    """the arithmetic of a training-path launch of this shape (fp32 unless PCC_TRAIN_BF16 / PCC_TRAIN_X3 ask otherwise)"""
+    return launch_mode(BF16, X3, rows, cin, cout, n_out, K, has_nbr) if BF16 or X3 else MODE_F32
 
 
 def _launch_conv(feats, w, bias, nbr, order, gmask, n_out):
     """feats: fp32, or an already cast bf16 copy (bf16 mode: one cast per tensor, shared by its consumers)"""
     L = _lib.lib()
     K, cin, cout = w.shape
+    rows = feats.shape[0]
+    mode = MODE_BF16 if feats.dtype == torch.bfloat16 else _mode(rows, cin, cout, n_out, K, nbr is not None)
     out = torch.empty((n_out, cout), dtype=torch.float32, device=feats.device)
-    if feats.dtype == torch.bfloat16 or _bf16_ok(feats.shape[0], cin):
-        wp = torch.empty(L.pcc_conv_packed_elems_bf16(K, cin, cout), dtype=torch.bfloat16, device=feats.device)
-        check(L.pcc_conv_pack_weights_bf16(ptr(w), K, cin, cout, ptr(wp), _lib.stream()))
-        x = feats if feats.dtype == torch.bfloat16 else feats.to(torch.bfloat16)
-        check(L.pcc_conv_fwd_bf16(ptr(x), feats.shape[0], cin, ptr(wp), ptr(bias), ptr(nbr), ptr(order), ptr(gmask), K, ptr(out),
-                                  n_out, cout, 0, None, None, _lib.stream()))
-        return out
-    if _x3_ok(feats.shape[0], cin, cout, n_out, K, nbr is not None):
-        wp = torch.empty(L.pcc_conv_packed_elems_x3(K, cin, cout), dtype=torch.bfloat16, device=feats.device)
-        check(L.pcc_conv_pack_weights_x3(ptr(w), K, cin, cout, ptr(wp), _lib.stream()))
-        check(L.pcc_conv_fwd_x3(ptr(feats), feats.shape[0], cin, ptr(wp), ptr(bias), ptr(nbr), ptr(order), ptr(gmask), K, ptr(out),
-                                n_out, cout, 0, None, None, _lib.stream()))
-        return out
-    check(L.pcc_conv_fwd(ptr(feats), feats.shape[0], cin, ptr(w), ptr(_packed(w)), ptr(bias), ptr(nbr), ptr(order), ptr(gmask), K,
-                         ptr(out), n_out, cout, 0, None, None, _lib.stream()))
+    wp = pack_weights(w, mode)
+    if mode == MODE_BF16:
+        x = feats.to(torch.bfloat16)
+        check(L.pcc_conv_fwd_bf16(ptr(x), rows, cin, ptr(wp), ptr(bias), ptr(nbr), ptr(order), ptr(gmask), K, ptr(out), n_out, cout,
+                                  0, None, None, _lib.stream()))
+    elif mode == MODE_X3:
+        check(L.pcc_conv_fwd_x3(ptr(feats), rows, cin, ptr(wp), ptr(bias), ptr(nbr), ptr(order), ptr(gmask), K, ptr(out), n_out, cout,
+                                0, None, None, _lib.stream()))
+    else:
+        check(L.pcc_conv_fwd(ptr(feats), rows, cin, ptr(w), ptr(wp), ptr(bias), ptr(nbr), ptr(order), ptr(gmask), K, ptr(out), n_out,
+                             cout, 0, None, None, _lib.stream()))
     return out
 
 
@@ -137,7 +121,7 @@ class SparseConvFn(torch.autograd.Function):
             b = None if b is None else b[:out_channels].contiguous()
         w = w.contiguous()
         nbr, order, gmask = _forward_map(in_map, out_map, ksize, transposed, feats.shape[1])
-        if _bf16_ok(feats.shape[0], feats.shape[1]):
+        if _mode(feats.shape[0], w.shape[1], w.shape[2], out_map.n, w.shape[0], nbr is not None) == MODE_BF16:
             feats = feats.to(torch.bfloat16)          # the one cast of this tensor: forward now, weight gradient later
         out = _launch_conv(feats, w, b, nbr, order, gmask, out_map.n)
         ctx.save_for_backward(feats, w)
@@ -213,7 +197,8 @@ class SparseConvFn(torch.autograd.Function):
 
         if ctx.needs_input_grad[0]:
             wt = w.transpose(1, 2)                                  # [K, cout, cin]
-            g = g_w if (ctx.needs_input_grad[1] and feats.dtype == torch.bfloat16 and cout % 64 == 0 and _bf16_ok(n_out, cout)) else dy
+            g = g_w if (ctx.needs_input_grad[1] and feats.dtype == torch.bfloat16 and cout % 64 == 0
+                        and _mode(n_out, cout, cin, n_in, K, ksize > 1) == MODE_BF16) else dy
             if cout % 32 and cout not in _THIN_CIN:                 # input widths of the thin forward kernel: _THIN_CIN
                 pad = next(c for c in _THIN_CIN if c >= cout) - cout
                 g = torch.cat([dy, torch.zeros((n_out, pad), dtype=torch.float32, device=dev)], dim=1).contiguous()

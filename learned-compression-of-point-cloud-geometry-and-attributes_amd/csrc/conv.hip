@@ -1171,39 +1171,30 @@ __global__ __launch_bounds__(256) void gather_sum27_kernel(const float* __restri
     for (int c = 0; c < COUT; ++c) o[c] = apply_act(acc[c] + (bias ? bias[c] : 0.0f), act);
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool HAS_NBR>
-static int launch_mfma_impl(const ConvArgs& a, hipStream_t st) {
-    static bool attr_set = false;
-    auto kern = conv_mfma_kernel<BM, BN, WAVES_M, WAVES_N, HAS_NBR>;
-    const int lds = conv_lds_bytes<BM, BN>();
-    if (!attr_set) {
-        PCC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
-    const int64_t tiles = (a.n_out + BM - 1) / BM;
-    const int64_t blocks = tiles * (a.coutp / BN);
-    PCC_REQUIRE(blocks < (1ll << 31), "conv: grid too large");
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, st, a);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
-}
+// ---------------------------------------------------------------------------------------------
+// launch plan: which kernel and template parameters run a forward launch.  plan_conv is the one place the rule lives:
+// the launches (conv_fwd) and their names (pcc_conv_kernel_name: bench.py's breakdown, the profiles) both follow it.
+// ---------------------------------------------------------------------------------------------
+enum ConvMode { CONV_F32 = 0, CONV_BF16 = 1, CONV_X3 = 2 };     // pcc_conv_fwd, pcc_conv_fwd_bf16, pcc_conv_fwd_x3
+static const char* const CONV_ENTRY[] = {"pcc_conv_fwd", "pcc_conv_fwd_bf16", "pcc_conv_fwd_x3"};
+static const char* const CONV_TAG[] = {"", "[bf16]", "[x3]"};
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int CCH, bool HAS_NBR, bool BF16 = false, bool X3 = false>
-static int launch_mfma_buf_impl(const ConvArgs& a, hipStream_t st) {
-    static bool attr_set = false;
-    auto kern = conv_mfma_buf_kernel<BM, BN, WAVES_M, WAVES_N, CCH, HAS_NBR, BF16, X3>;
-    const int lds = conv_lds_bytes<BM, BN, X3>();
-    if (!attr_set) {
-        PCC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
-    const int64_t tiles = (a.n_out + BM - 1) / BM;
-    const int64_t blocks = tiles * (a.coutp / BN);
-    PCC_REQUIRE(blocks < (1ll << 31), "conv: grid too large");
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, st, a);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
-}
+enum ConvFamily { FAM_THIN, FAM_SMALL, FAM_BUF, FAM_GLOBAL };   // conv_thin / conv_small / conv_mfma_buf / conv_mfma kernel
+
+struct ConvPlan {
+    ConvFamily family;
+    int bm, bn, wm, wn;   // MFMA kernels: output rows x columns per workgroup, waves along each
+    int cch;              // buffer kernel: chunks of 32 input channels (bf16: 64)
+    int sc, ns;           // small kernel: chunks per step, LDS stages
+    int cpt;              // thin kernel: output channels per thread
+};
+
+// Workgroups of 64 x 128 that fill the chip once (256 CUs x 3): 128-wide launches below it take 64 x 64 tiles
+constexpr int64_t FILL_WGS = 768;
+// fp32 128-wide launches from FILL_WGS to this take 32-row tiles
+constexpr int64_t ROW32_MAX_WGS = 3000;
+
+static inline int round_up32(int v) { return (v + 31) / 32 * 32; }
 
 // 32-bit buffer offsets: every operand the buffer path addresses must stay below BUF_OOB bytes
 static bool fits_buffer_path(const ConvArgs& a) {
@@ -1218,21 +1209,6 @@ static int conv_path() {
     return path;
 }
 
-template <int SC, int NS>
-static int launch_small_impl(const ConvArgs& a, hipStream_t st) {
-    static bool attr_set = false;
-    auto kern = conv_small_kernel<SC, NS>;
-    const int lds = conv_small_lds_bytes<SC, NS>();
-    if (!attr_set) {
-        PCC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
-    const int64_t blocks = ((a.n_out + 31) / 32) * (a.coutp / 32);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, st, a);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
-}
-
 // The small-launch kernel takes a map convolution of at most PCC_CONV_SMALL_MAX (default 640; 0 = never) 32 x 32 output
 // tiles — twice that for outputs narrower than 128 columns, whose ordinary kernel (128-row tiles) fills the chip later.
 // Measured on MI355X (tools/conv_small_bench.py, one launch): 128 -> 128 on 56 .. 1,136 rows 27 us against 66, 64 -> 64
@@ -1243,104 +1219,215 @@ static int64_t small_max_value() {
     if (g_small_max < 0) { const char* e = getenv("PCC_CONV_SMALL_MAX"); g_small_max = e ? atoll(e) : 640; }
     return g_small_max;
 }
-static bool small_launch(const ConvArgs& a) {
-    const int64_t small_max = small_max_value() * (a.coutp % 128 == 0 ? 1 : 2);
-    return a.nbr && conv_path() == 0 && a.cin % 32 == 0 && a.coutp % 32 == 0 && ((a.n_out + 31) / 32) * (a.coutp / 32) <= small_max;
+
+// input widths of the scalar thin kernel (3, 6, 12, 24: C_bottleneck * 3 / 2 of a hyperprior over a narrow tensor; 4: the
+// two-hyperprior variant codes the 2-channel q-map, model/entropy_models.py:140-147); launch_thin_cin switches over them
+static bool thin_cin(int cin) {
+    for (int c : {1, 2, 3, 4, 6, 8, 12, 16, 24})
+        if (cin == c) return true;
+    return false;
 }
 
-static int launch_small(const ConvArgs& a, hipStream_t st) {
-    const int cch = a.cin / 32;
-    // a step of four chunks (27 barriers for 128 channels instead of 54) while one workgroup per CU — 100 KB of LDS — holds
-    // the launch; else two chunks per step at 52 KB (three workgroups per CU); odd chunk counts one chunk per step
-    const int64_t wgs = ((a.n_out + 31) / 32) * (a.coutp / 32);
-    if (cch % 4 == 0 && wgs <= 256) return launch_small_impl<4, 3>(a, st);
-    return cch % 2 == 0 ? launch_small_impl<2, 3>(a, st) : launch_small_impl<1, 8>(a, st);
+// The argument checks every entry makes before it looks at the row count
+static int check_shape(const ConvArgs& a, ConvMode mode, const char* who) {
+    PCC_REQUIRE(a.K >= 1 && a.K <= 27, "%s: K=%d out of range", who, a.K);
+    if (mode == CONV_F32) PCC_REQUIRE(a.cin % 32 != 0 || a.cin <= 256, "%s: MFMA path supports cin <= 256 (got %d)", who, a.cin);
+    if (mode == CONV_BF16) PCC_REQUIRE(a.cin % 64 == 0 && a.cin <= 256, "%s: cin must be a multiple of 64 up to 256 (got %d)", who, a.cin);
+    if (mode == CONV_X3) PCC_REQUIRE(a.cin % 32 == 0 && a.cin <= 256, "%s: cin must be a multiple of 32 up to 256 (got %d)", who, a.cin);
+    PCC_REQUIRE(a.nbr != nullptr || (a.K == 1 && a.n_in == a.n_out), "%s: nbr == NULL needs K == 1 and n_in == n_out", who);
+    return PCC_OK;
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N>
-static int launch_mfma(const ConvArgs& a, hipStream_t st) {
-    const int path = conv_path();
-    if (path == 0 && fits_buffer_path(a)) {
-#define PCC_BUF_CASE(C)                                                                                        \
-    case C:                                                                                                    \
-        return a.nbr ? launch_mfma_buf_impl<BM, BN, WAVES_M, WAVES_N, C, true>(a, st)                          \
-                     : launch_mfma_buf_impl<BM, BN, WAVES_M, WAVES_N, C, false>(a, st);
-        switch (a.cin / 32) {
-            PCC_BUF_CASE(1) PCC_BUF_CASE(2) PCC_BUF_CASE(3) PCC_BUF_CASE(4)
-            PCC_BUF_CASE(5) PCC_BUF_CASE(6) PCC_BUF_CASE(7) PCC_BUF_CASE(8)
-            default: break;
+// The kernel and tile a launch of `mode` runs: PCC_OK, or the reason (set_error) and code why `mode` cannot run the shape.
+// The accumulation order of an output element does not depend on the kernel or tile, so every choice is bit-identical.
+static int plan_conv(const ConvArgs& a, ConvMode mode, ConvPlan& p, const char* who) {
+    p = ConvPlan{};
+    if (mode == CONV_F32 && a.cin % 32 != 0) {
+        if (!thin_cin(a.cin)) {
+            pcc::set_error("%s: unsupported cin=%d (need a multiple of 32 or one of 1,2,3,4,6,8,12,16,24)", who, a.cin);
+            return PCC_ERR_UNSUPPORTED;
         }
-#undef PCC_BUF_CASE
+        const size_t lds = (size_t)a.K * a.cin * a.cout * sizeof(float);
+        PCC_REQUIRE(lds <= 160 * 1024, "conv(thin): weights %zu B exceed the 160 KB of LDS (cin=%d cout=%d K=%d)", lds, a.cin, a.cout, a.K);
+        p.family = FAM_THIN;
+        p.cpt = (a.cout % 8 == 0) ? 8 : (a.cout % 4 == 0) ? 4 : (a.cout % 2 == 0) ? 2 : 1;   // the largest of 8, 4, 2, 1 dividing cout
+        return PCC_OK;
     }
-    return a.nbr ? launch_mfma_impl<BM, BN, WAVES_M, WAVES_N, true>(a, st) : launch_mfma_impl<BM, BN, WAVES_M, WAVES_N, false>(a, st);
-}
-
-template <int BM, int BN, int WAVES_M, int WAVES_N>
-static int launch_mfma_bf16(const ConvArgs& a, hipStream_t st) {
-#define PCC_BF16_CASE(C)                                                                                       \
-    case C:                                                                                                    \
-        return a.nbr ? launch_mfma_buf_impl<BM, BN, WAVES_M, WAVES_N, C, true, true>(a, st)                    \
-                     : launch_mfma_buf_impl<BM, BN, WAVES_M, WAVES_N, C, false, true>(a, st);
-    switch (a.cin / 64) {
-        PCC_BF16_CASE(1) PCC_BF16_CASE(2) PCC_BF16_CASE(3) PCC_BF16_CASE(4)
-        default: break;
+    const bool wide = a.coutp % 128 == 0;
+    p.family = FAM_BUF;
+    p.cch = a.cin / (mode == CONV_BF16 ? 64 : 32);
+    if (mode == CONV_F32) {
+        const bool buffer = conv_path() == 0 && fits_buffer_path(a);
+        // Launches of a few hundred 32 x 32 tiles: one 16 x 16 MFMA block per wave, deep gather pipeline (conv_small_kernel).
+        // A step of four chunks (27 barriers for 128 channels instead of 54) while one workgroup per CU — 100 KB of LDS —
+        // holds the launch; else two chunks per step at 52 KB (three workgroups per CU); odd chunk counts one chunk per step.
+        const int64_t wgs32 = ((a.n_out + 31) / 32) * (a.coutp / 32);
+        if (a.nbr && buffer && wgs32 <= small_max_value() * (wide ? 1 : 2)) {
+            p.family = FAM_SMALL;
+            p.sc = (p.cch % 4 == 0 && wgs32 <= 256) ? 4 : p.cch % 2 == 0 ? 2 : 1;
+            p.ns = p.sc == 1 ? 8 : 3;
+            return PCC_OK;
+        }
+        if (!buffer) p.family = FAM_GLOBAL;
+    } else if (mode == CONV_BF16) {
+        PCC_REQUIRE((uint64_t)a.n_in * a.cin * 2 <= BUF_OOB && (uint64_t)a.n_out * a.K * 4 <= BUF_OOB,
+                    "%s: operands of 4 GiB and more are not supported", who);
+    } else {
+        PCC_REQUIRE((uint64_t)a.n_in * a.cin * 4 <= BUF_OOB && (uint64_t)a.n_out * a.K * 4 <= BUF_OOB &&
+                    (uint64_t)a.K * a.cin * a.coutp * 6 <= BUF_OOB, "%s: operands of 4 GiB and more are not supported", who);
     }
-#undef PCC_BF16_CASE
-    pcc::set_error("pcc_conv_fwd_bf16: cin=%d not supported (multiples of 64 up to 256)", a.cin);
+    // Tiles, measured on MI355X.  128-wide outputs run best with 64-row tiles (48 KB of LDS per
+    // workgroup -> 3 workgroups per CU, twice the tiles per launch -> less tail loss on mid-size layers); launches that would
+    // not fill the chip with them are split into 64-wide column tiles (twice the workgroups, half the MFMAs per step).  fp32
+    // mid-size launches (one to three rounds of 64 x 128 workgroups) take 32-row tiles — all four waves on one 32-row MFMA
+    // tile, each a 32-column slice: twice the workgroups at 40 KB of LDS (four per CU), so the launch's last round is fuller
+    // and a workgroup executes exactly the offsets its own 32 rows need (config-2 frame: the 72 k-row layers 0.34-0.51 ->
+    // 0.27-0.47 ms, no gain from 233 k rows on, a loss on the 1.26 M-row layers).  64-wide outputs take 128-row tiles (half
+    // the weight-slab traffic per MFMA).  x3: with the matrix-pipe time at 3/8 the loop waits for its gathers, so occupancy
+    // decides — the three-plane weight slab makes a 64 x 128 tile 64 KB of LDS (two workgroups per CU) and a 64 x 64 tile
+    // 40 KB (four); 64-wide outputs: 64 x 64 tiles 5.2 ms against 5.75 for 128 x 64 on the 5.16 M-row layers.
+    const int64_t wgs128 = ((a.n_out + 63) / 64) * (a.coutp / 128);
+    auto tile = [&](int bm, int bn, int wm, int wn) { p.bm = bm; p.bn = bn; p.wm = wm; p.wn = wn; return PCC_OK; };
+    if (wide && wgs128 < FILL_WGS) return tile(64, 64, 2, 2);
+    if (wide && mode == CONV_F32 && wgs128 < ROW32_MAX_WGS) return tile(32, 128, 1, 4);
+    if (wide) return tile(64, 128, 2, 2);
+    if (a.coutp % 64 == 0) return mode == CONV_X3 ? tile(64, 64, 2, 2) : tile(128, 64, 2, 2);
+    if (mode != CONV_X3) return tile(128, 32, 4, 1);
+    pcc::set_error("%s: cout=%d not supported (output width rounded up to 32 must be a multiple of 64)", who, a.cout);
     return PCC_ERR_UNSUPPORTED;
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N>
-static int launch_mfma_x3(const ConvArgs& a, hipStream_t st) {
-#define PCC_X3_CASE(C)                                                                                         \
-    case C:                                                                                                    \
-        return a.nbr ? launch_mfma_buf_impl<BM, BN, WAVES_M, WAVES_N, C, true, false, true>(a, st)             \
-                     : launch_mfma_buf_impl<BM, BN, WAVES_M, WAVES_N, C, false, false, true>(a, st);
-    switch (a.cin / 32) {
-        PCC_X3_CASE(1) PCC_X3_CASE(2) PCC_X3_CASE(3) PCC_X3_CASE(4)
-        PCC_X3_CASE(5) PCC_X3_CASE(6) PCC_X3_CASE(7) PCC_X3_CASE(8)
-        default: break;
+// Launches KERN; the first launch with `lds_limit` != 0 raises the kernel's dynamic-LDS limit to it (once per instantiation)
+template <auto KERN>
+static int launch(int64_t blocks, int threads, size_t lds, size_t lds_limit, const ConvArgs& a, hipStream_t st) {
+    static bool limit_set = false;
+    if (lds_limit && !limit_set) {
+        PCC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
+        limit_set = true;
     }
-#undef PCC_X3_CASE
-    pcc::set_error("pcc_conv_fwd_x3: cin=%d not supported (multiples of 32 up to 256)", a.cin);
-    return PCC_ERR_UNSUPPORTED;
-}
-
-template <int CIN, int CPT>
-static int launch_thin_cpt(const ConvArgs& a, unsigned nb, size_t lds, hipStream_t st) {
-    auto kern = conv_thin_kernel<CIN, CPT>;
-    if (lds > 64 * 1024) {                        // beyond the default dynamic-LDS limit (24 -> 32 with 27 offsets: 81 KB)
-        static bool attr_set = false;
-        if (!attr_set) {
-            PCC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set = true;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, st, a);
+    PCC_REQUIRE(blocks < (1ll << 31), "conv: grid too large");
+    hipLaunchKernelGGL(KERN, dim3((unsigned)blocks), dim3(threads), lds, st, a);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
 }
 
+template <ConvMode M, int BM, int BN, int WM, int WN, int CCH>
+static int launch_buf(int64_t blocks, const ConvArgs& a, hipStream_t st) {
+    constexpr bool BF16 = M == CONV_BF16, X3 = M == CONV_X3;
+    if constexpr (BF16 && CCH > 4) {
+        return PCC_ERR_UNSUPPORTED;                                 // (cin <= 256: never planned)
+    } else {
+        constexpr int lds = conv_lds_bytes<BM, BN, X3>();
+        return a.nbr ? launch<conv_mfma_buf_kernel<BM, BN, WM, WN, CCH, true, BF16, X3>>(blocks, 256, lds, lds, a, st)
+                     : launch<conv_mfma_buf_kernel<BM, BN, WM, WN, CCH, false, BF16, X3>>(blocks, 256, lds, lds, a, st);
+    }
+}
+
+// the channel-chunk switch (fp32 plans may take the 64-bit-addressed kernel instead)
+template <ConvMode M, int BM, int BN, int WM, int WN>
+static int launch_mfma(const ConvPlan& p, const ConvArgs& a, hipStream_t st) {
+    const int64_t blocks = (a.n_out + BM - 1) / BM * (a.coutp / BN);
+    if constexpr (M == CONV_F32) {
+        if (p.family == FAM_GLOBAL) {
+            constexpr int lds = conv_lds_bytes<BM, BN>();
+            return a.nbr ? launch<conv_mfma_kernel<BM, BN, WM, WN, true>>(blocks, 256, lds, lds, a, st)
+                         : launch<conv_mfma_kernel<BM, BN, WM, WN, false>>(blocks, 256, lds, lds, a, st);
+        }
+    }
+    switch (p.cch) {
+        case 1: return launch_buf<M, BM, BN, WM, WN, 1>(blocks, a, st);
+        case 2: return launch_buf<M, BM, BN, WM, WN, 2>(blocks, a, st);
+        case 3: return launch_buf<M, BM, BN, WM, WN, 3>(blocks, a, st);
+        case 4: return launch_buf<M, BM, BN, WM, WN, 4>(blocks, a, st);
+        case 5: return launch_buf<M, BM, BN, WM, WN, 5>(blocks, a, st);
+        case 6: return launch_buf<M, BM, BN, WM, WN, 6>(blocks, a, st);
+        case 7: return launch_buf<M, BM, BN, WM, WN, 7>(blocks, a, st);
+        case 8: return launch_buf<M, BM, BN, WM, WN, 8>(blocks, a, st);
+        default: return PCC_ERR_UNSUPPORTED;
+    }
+}
+
+// the tiles each mode plans (and no others are instantiated)
+template <ConvMode M>
+static int launch_tile(const ConvPlan& p, const ConvArgs& a, hipStream_t st) {
+    if (p.bm == 64 && p.bn == 64) return launch_mfma<M, 64, 64, 2, 2>(p, a, st);
+    if (p.bm == 64 && p.bn == 128) return launch_mfma<M, 64, 128, 2, 2>(p, a, st);
+    if constexpr (M == CONV_F32)
+        if (p.bm == 32) return launch_mfma<M, 32, 128, 1, 4>(p, a, st);
+    if constexpr (M != CONV_X3) {
+        if (p.bn == 64) return launch_mfma<M, 128, 64, 2, 2>(p, a, st);
+        if (p.bn == 32) return launch_mfma<M, 128, 32, 4, 1>(p, a, st);
+    }
+    return PCC_ERR_UNSUPPORTED;
+}
+
+template <int SC, int NS>
+static int launch_small(const ConvArgs& a, hipStream_t st) {
+    constexpr int lds = conv_small_lds_bytes<SC, NS>();
+    return launch<conv_small_kernel<SC, NS>>(((a.n_out + 31) / 32) * (a.coutp / 32), 512, lds, lds, a, st);
+}
+
 template <int CIN>
-static int launch_thin(const ConvArgs& a, hipStream_t st) {
+static int launch_thin(const ConvPlan& p, const ConvArgs& a, hipStream_t st) {
     const size_t lds = (size_t)a.K * CIN * a.cout * sizeof(float);
-    PCC_REQUIRE(lds <= 160 * 1024, "conv(thin): weights %zu B exceed the 160 KB of LDS (cin=%d cout=%d K=%d)", lds, CIN, a.cout, a.K);
-    // channels per thread: the largest of 8, 4, 2, 1 dividing cout
-    const int cpt = (a.cout % 8 == 0) ? 8 : (a.cout % 4 == 0) ? 4 : (a.cout % 2 == 0) ? 2 : 1;
     // every block stages the whole weight tensor into LDS first (27.6 KB for 2 -> 128): a few resident blocks per CU
     // that stride over the rows, not one block per 256 outputs
-    const unsigned nb = blocks_for(a.n_out * (a.cout / cpt), 256, lds >= 4096 ? 2048u : (1u << 20));
-    if (cpt == 8) return launch_thin_cpt<CIN, 8>(a, nb, lds, st);
-    if (cpt == 4) return launch_thin_cpt<CIN, 4>(a, nb, lds, st);
-    if (cpt == 2) return launch_thin_cpt<CIN, 2>(a, nb, lds, st);
-    return launch_thin_cpt<CIN, 1>(a, nb, lds, st);
+    const unsigned nb = blocks_for(a.n_out * (a.cout / p.cpt), 256, lds >= 4096 ? 2048u : (1u << 20));
+    // beyond the default dynamic-LDS limit (24 -> 32 with 27 offsets: 81 KB) the kernel's limit is raised to 160 KB
+    const size_t limit = lds > 64 * 1024 ? 160 * 1024 : 0;
+    if (p.cpt == 8) return launch<conv_thin_kernel<CIN, 8>>(nb, 256, lds, limit, a, st);
+    if (p.cpt == 4) return launch<conv_thin_kernel<CIN, 4>>(nb, 256, lds, limit, a, st);
+    if (p.cpt == 2) return launch<conv_thin_kernel<CIN, 2>>(nb, 256, lds, limit, a, st);
+    return launch<conv_thin_kernel<CIN, 1>>(nb, 256, lds, limit, a, st);
+}
+
+static int launch_thin_cin(const ConvPlan& p, const ConvArgs& a, hipStream_t st) {
+    switch (a.cin) {
+        case 1: return launch_thin<1>(p, a, st);
+        case 2: return launch_thin<2>(p, a, st);
+        case 3: return launch_thin<3>(p, a, st);
+        case 4: return launch_thin<4>(p, a, st);
+        case 6: return launch_thin<6>(p, a, st);
+        case 8: return launch_thin<8>(p, a, st);
+        case 12: return launch_thin<12>(p, a, st);
+        case 16: return launch_thin<16>(p, a, st);
+        case 24: return launch_thin<24>(p, a, st);
+        default: return PCC_ERR_UNSUPPORTED;
+    }
+}
+
+// The forward of every mode: checks, plan, launch
+static int conv_fwd(ConvMode mode, const ConvArgs& a, void* stream) {
+    const char* who = CONV_ENTRY[mode];
+    int rc = check_shape(a, mode, who);
+    if (rc != PCC_OK) return rc;
+    PCC_REQUIRE(a.act >= 0 && a.act <= 2, "%s: bad activation %d", who, a.act);
+    if (mode == CONV_F32 && a.n_out <= 0) return PCC_OK;             // (the fp32 entry checks its weights for rows only)
+    if (mode != CONV_F32 || a.cin % 32 == 0) {
+        PCC_REQUIRE(a.wp != nullptr, "%s: MFMA path (cin=%d) needs packed weights", who, a.cin);
+        PCC_REQUIRE(((reinterpret_cast<uintptr_t>(a.fin) | reinterpret_cast<uintptr_t>(a.wp)) & 15) == 0,
+                    "%s: fin and w_packed must be 16-byte aligned (16-byte LDS-DMA loads)", who);
+    } else {
+        PCC_REQUIRE(a.w != nullptr, "%s: thin path (cin=%d) needs raw weights", who, a.cin);
+    }
+    if (a.n_out <= 0) return PCC_OK;
+    ConvPlan p;
+    if ((rc = plan_conv(a, mode, p, who)) != PCC_OK) return rc;
+    hipStream_t st = as_stream(stream);
+    switch (p.family) {
+        case FAM_THIN: return launch_thin_cin(p, a, st);
+        case FAM_SMALL:
+            if (p.sc == 4) return launch_small<4, 3>(a, st);
+            return p.sc == 2 ? launch_small<2, 3>(a, st) : launch_small<1, 8>(a, st);
+        default:
+            if (mode == CONV_BF16) return launch_tile<CONV_BF16>(p, a, st);
+            return mode == CONV_X3 ? launch_tile<CONV_X3>(p, a, st) : launch_tile<CONV_F32>(p, a, st);
+    }
 }
 
 }  // namespace pcc
 
 using namespace pcc;
-
-static inline int round_up32(int v) { return (v + 31) / 32 * 32; }
 
 extern "C" {
 
@@ -1375,26 +1462,8 @@ int pcc_conv_pack_weights_bf16(const float* w, int32_t K, int32_t cin, int32_t c
 int pcc_conv_fwd_bf16(const uint16_t* fin, int64_t n_in, int32_t cin, const uint16_t* w_packed, const float* bias, const int32_t* nbr,
                       const int32_t* order, const uint32_t* group_mask32, int32_t K, float* fout, int64_t n_out, int32_t cout,
                       int32_t act, const float* film, const float* residual, void* stream) {
-    PCC_REQUIRE(K >= 1 && K <= 27, "pcc_conv_fwd_bf16: K=%d out of range", K);
-    PCC_REQUIRE(cin % 64 == 0 && cin <= 256, "pcc_conv_fwd_bf16: cin must be a multiple of 64 up to 256 (got %d)", cin);
-    PCC_REQUIRE(nbr != nullptr || (K == 1 && n_in == n_out), "pcc_conv_fwd_bf16: nbr == NULL needs K == 1 and n_in == n_out");
-    PCC_REQUIRE(act >= 0 && act <= 2, "pcc_conv_fwd_bf16: bad activation %d", act);
-    PCC_REQUIRE(w_packed != nullptr, "pcc_conv_fwd_bf16: packed weights required");
-    PCC_REQUIRE(((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(w_packed)) & 15) == 0,
-                "pcc_conv_fwd_bf16: fin and w_packed must be 16-byte aligned (16-byte LDS-DMA loads)");
-    if (n_out <= 0) return PCC_OK;
-    ConvArgs a;
-    a.fin = reinterpret_cast<const float*>(fin); a.w = nullptr; a.wp = reinterpret_cast<const float*>(w_packed); a.bias = bias;
-    a.nbr = nbr; a.order = order; a.gmask = group_mask32; a.fout = fout; a.film = film; a.residual = residual;
-    a.n_in = n_in; a.n_out = n_out; a.cin = cin; a.cout = cout; a.coutp = round_up32(cout); a.K = K; a.act = act; a.bf16 = 1;
-    PCC_REQUIRE((uint64_t)n_in * cin * 2 <= BUF_OOB && (uint64_t)n_out * K * 4 <= BUF_OOB,
-                "pcc_conv_fwd_bf16: operands of 4 GiB and more are not supported");
-    hipStream_t st = as_stream(stream);
-    const int64_t wgs128 = ((a.n_out + 63) / 64) * (a.coutp / 128);
-    if (a.coutp % 128 == 0 && wgs128 < 768) return launch_mfma_bf16<64, 64, 2, 2>(a, st);
-    if (a.coutp % 128 == 0) return launch_mfma_bf16<64, 128, 2, 2>(a, st);
-    if (a.coutp % 64 == 0) return launch_mfma_bf16<128, 64, 2, 2>(a, st);
-    return launch_mfma_bf16<128, 32, 4, 1>(a, st);
+    return conv_fwd(CONV_BF16, {reinterpret_cast<const float*>(fin), nullptr, reinterpret_cast<const float*>(w_packed), bias, nbr, order,
+                                group_mask32, fout, film, residual, n_in, n_out, cin, cout, round_up32(cout), K, act, 1}, stream);
 }
 
 int64_t pcc_conv_packed_elems_x3(int32_t K, int32_t cin, int32_t cout) {
@@ -1414,31 +1483,8 @@ int pcc_conv_pack_weights_x3(const float* w, int32_t K, int32_t cin, int32_t cou
 int pcc_conv_fwd_x3(const float* fin, int64_t n_in, int32_t cin, const uint16_t* w_packed, const float* bias, const int32_t* nbr,
                     const int32_t* order, const uint32_t* group_mask32, int32_t K, float* fout, int64_t n_out, int32_t cout,
                     int32_t act, const float* film, const float* residual, void* stream) {
-    PCC_REQUIRE(K >= 1 && K <= 27, "pcc_conv_fwd_x3: K=%d out of range", K);
-    PCC_REQUIRE(cin % 32 == 0 && cin <= 256, "pcc_conv_fwd_x3: cin must be a multiple of 32 up to 256 (got %d)", cin);
-    PCC_REQUIRE(nbr != nullptr || (K == 1 && n_in == n_out), "pcc_conv_fwd_x3: nbr == NULL needs K == 1 and n_in == n_out");
-    PCC_REQUIRE(act >= 0 && act <= 2, "pcc_conv_fwd_x3: bad activation %d", act);
-    PCC_REQUIRE(w_packed != nullptr, "pcc_conv_fwd_x3: packed weights required");
-    PCC_REQUIRE(((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(w_packed)) & 15) == 0,
-                "pcc_conv_fwd_x3: fin and w_packed must be 16-byte aligned (16-byte LDS-DMA loads)");
-    if (n_out <= 0) return PCC_OK;
-    ConvArgs a;
-    a.fin = fin; a.w = nullptr; a.wp = reinterpret_cast<const float*>(w_packed); a.bias = bias;
-    a.nbr = nbr; a.order = order; a.gmask = group_mask32; a.fout = fout; a.film = film; a.residual = residual;
-    a.n_in = n_in; a.n_out = n_out; a.cin = cin; a.cout = cout; a.coutp = round_up32(cout); a.K = K; a.act = act; a.bf16 = 0;
-    PCC_REQUIRE((uint64_t)n_in * cin * 4 <= BUF_OOB && (uint64_t)n_out * K * 4 <= BUF_OOB && (uint64_t)K * cin * a.coutp * 6 <= BUF_OOB,
-                "pcc_conv_fwd_x3: operands of 4 GiB and more are not supported");
-    hipStream_t st = as_stream(stream);
-    // Tile shapes, measured on the config-2 frame: with the matrix-pipe time at 3/8 the loop waits for its gathers, so
-    // occupancy decides — the three-plane weight slab makes a 64 x 128 tile 64 KB of LDS (two workgroups per CU) and a
-    // 64 x 64 tile 40 KB (four).  64-wide outputs: 64 x 64 tiles 5.2 ms against 5.75 for 128 x 64 on the 5.16 M-row layers;
-    // 128-wide outputs: 64 x 128 tiles 4.95-5.15 ms against 5.2-5.35 for 64 x 64 (which gathers every row twice).
-    const int64_t wgs128 = ((a.n_out + 63) / 64) * (a.coutp / 128);
-    if (a.coutp % 128 == 0 && wgs128 < 768) return launch_mfma_x3<64, 64, 2, 2>(a, st);
-    if (a.coutp % 128 == 0) return launch_mfma_x3<64, 128, 2, 2>(a, st);
-    if (a.coutp % 64 == 0) return launch_mfma_x3<64, 64, 2, 2>(a, st);
-    pcc::set_error("pcc_conv_fwd_x3: cout=%d not supported (output width rounded up to 32 must be a multiple of 64)", cout);
-    return PCC_ERR_UNSUPPORTED;
+    return conv_fwd(CONV_X3, {fin, nullptr, reinterpret_cast<const float*>(w_packed), bias, nbr, order, group_mask32, fout, film,
+                              residual, n_in, n_out, cin, cout, round_up32(cout), K, act, 0}, stream);
 }
 
 int pcc_im2col_thin(const float* fin, int32_t cin, const int32_t* nbr, int64_t n_out, int32_t K, float* out, int32_t k2,
@@ -1484,61 +1530,29 @@ int64_t pcc_conv_small_max(int64_t workgroups) {
 int pcc_conv_fwd(const float* fin, int64_t n_in, int32_t cin, const float* w, const float* w_packed, const float* bias,
                  const int32_t* nbr, const int32_t* order, const uint32_t* group_mask32, int32_t K, float* fout,
                  int64_t n_out, int32_t cout, int32_t act, const float* film, const float* residual, void* stream) {
-    PCC_REQUIRE(K >= 1 && K <= 27, "pcc_conv_fwd: K=%d out of range", K);
-    PCC_REQUIRE(cin % 32 != 0 || cin <= 256, "pcc_conv_fwd: MFMA path supports cin <= 256 (got %d)", cin);
-    PCC_REQUIRE(nbr != nullptr || (K == 1 && n_in == n_out), "pcc_conv_fwd: nbr == NULL needs K == 1 and n_in == n_out");
-    PCC_REQUIRE(act >= 0 && act <= 2, "pcc_conv_fwd: bad activation %d", act);
-    if (n_out <= 0) return PCC_OK;
-    ConvArgs a;
-    a.fin = fin; a.w = w; a.wp = w_packed; a.bias = bias; a.nbr = nbr; a.order = order; a.gmask = group_mask32; a.fout = fout;
-    a.film = film; a.residual = residual; a.n_in = n_in; a.n_out = n_out; a.cin = cin; a.cout = cout;
-    a.coutp = round_up32(cout); a.K = K; a.act = act; a.bf16 = 0;
-    hipStream_t st = as_stream(stream);
-    if (cin % 32 == 0) {
-        PCC_REQUIRE(w_packed != nullptr, "pcc_conv_fwd: MFMA path (cin=%d) needs packed weights", cin);
-        PCC_REQUIRE(((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(w_packed)) & 15) == 0,
-                    "pcc_conv_fwd: fin and w_packed must be 16-byte aligned (16-byte LDS-DMA loads)");
-        // Row-tile height, measured on MI355X: 128-wide outputs run best with 64-row tiles (48 KB of LDS per
-        // workgroup -> 3 workgroups per CU, twice the tiles per launch -> less tail loss on mid-size layers);
-        // 64-wide outputs with 128-row tiles (half the weight-slab traffic per MFMA).  PCC_CONV_BM=64|128
-        // forces one height for A/B testing.
-        static int bm = -1;
-        if (bm < 0) { const char* e = getenv("PCC_CONV_BM"); bm = e ? atoi(e) : 0; }
-        // Launches of a few hundred 32 x 32 tiles: one 16 x 16 MFMA block per wave, deep gather pipeline (conv_small_kernel)
-        if (bm == 0 && small_launch(a) && fits_buffer_path(a)) return launch_small(a, st);
-        // Launches that would not fill the chip (256 CUs x 3 workgroups) with 128-wide tiles are split
-        // into 64-wide column tiles: twice the workgroups, half the MFMAs per step and workgroup.  The
-        // accumulation order of an output element does not depend on the tile shape, so results are
-        // bit-identical across configurations.
-        const int64_t wgs128 = ((a.n_out + 63) / 64) * (a.coutp / 128);
-        if (a.coutp % 128 == 0 && bm == 0 && wgs128 < 768) return launch_mfma<64, 64, 2, 2>(a, st);
-        // Mid-size launches (one to three rounds of 64 x 128 workgroups on 256 CUs x 3) take 32-row tiles — all four waves on
-        // one 32-row MFMA tile, each a 32-column slice: twice the workgroups at 40 KB of LDS (four per CU), so the launch's
-        // last round is fuller, and a workgroup executes exactly the offsets its own 32 rows need.  Measured on the config-2
-        // frame: the 72 k-row layers 0.34-0.51 -> 0.27-0.47 ms (12 launches), no gain from 233 k rows on, a loss on the
-        // 1.26 M-row layers (more weight-slab traffic per MFMA).  PCC_CONV_BM32_MAX=<workgroups> moves the switch (0 = off).
-        static int64_t bm32_max = -1;
-        if (bm32_max < 0) { const char* e = getenv("PCC_CONV_BM32_MAX"); bm32_max = e ? atoll(e) : 3000; }
-        if (a.coutp % 128 == 0 && (bm == 32 || (bm == 0 && wgs128 >= 768 && wgs128 < bm32_max))) return launch_mfma<32, 128, 1, 4>(a, st);
-        if (a.coutp % 128 == 0) return bm == 128 ? launch_mfma<128, 128, 2, 2>(a, st) : launch_mfma<64, 128, 2, 2>(a, st);
-        if (a.coutp % 64 == 0) return bm == 64 ? launch_mfma<64, 64, 2, 2>(a, st) : launch_mfma<128, 64, 2, 2>(a, st);
-        return launch_mfma<128, 32, 4, 1>(a, st);
-    }
-    PCC_REQUIRE(w != nullptr, "pcc_conv_fwd: thin path (cin=%d) needs raw weights", cin);
-    switch (cin) {
-        case 1: return launch_thin<1>(a, st);
-        case 2: return launch_thin<2>(a, st);
-        case 3: return launch_thin<3>(a, st);        // 3, 6, 12, 24: C_bottleneck * 3 / 2 of a hyperprior over a narrow tensor
-        case 4: return launch_thin<4>(a, st);        // (the two-hyperprior variant codes the 2-channel q-map: model/entropy_models.py:140-147)
-        case 6: return launch_thin<6>(a, st);
-        case 8: return launch_thin<8>(a, st);
-        case 12: return launch_thin<12>(a, st);
-        case 16: return launch_thin<16>(a, st);
-        case 24: return launch_thin<24>(a, st);
-        default:
-            pcc::set_error("pcc_conv_fwd: unsupported cin=%d (need a multiple of 32 or one of 1,2,3,4,6,8,12,16,24)", cin);
-            return PCC_ERR_UNSUPPORTED;
-    }
+    return conv_fwd(CONV_F32, {fin, w, w_packed, bias, nbr, order, group_mask32, fout, film, residual, n_in, n_out, cin, cout,
+                               round_up32(cout), K, act, 0}, stream);
+}
+
+int pcc_conv_kernel_name(int32_t mode, int64_t n_in, int32_t cin, int32_t cout, int64_t n_out, int32_t K, int32_t has_nbr,
+                         char* buf, int32_t len) {
+    PCC_REQUIRE(mode >= CONV_F32 && mode <= CONV_X3, "pcc_conv_kernel_name: bad mode %d", mode);
+    static const int32_t any_map = 0;                      // the plan reads only whether a map is given
+    ConvArgs a = {};
+    a.nbr = has_nbr ? &any_map : nullptr;
+    a.n_in = n_in; a.n_out = n_out; a.cin = cin; a.cout = cout; a.coutp = round_up32(cout); a.K = K;
+    const ConvMode m = ConvMode(mode);
+    ConvPlan p;
+    if (check_shape(a, m, CONV_ENTRY[m]) != PCC_OK || plan_conv(a, m, p, CONV_ENTRY[m]) != PCC_OK) return PCC_ERR_UNSUPPORTED;
+    if (buf == nullptr) return PCC_OK;
+    const char* tf = has_nbr ? "true" : "false";
+    int n;
+    if (p.family == FAM_THIN) n = snprintf(buf, len, "conv_thin_kernel<%d, %d>", cin, p.cpt);
+    else if (p.family == FAM_SMALL) n = snprintf(buf, len, "conv_small_kernel<%d, %d>", p.sc, p.ns);
+    else if (p.family == FAM_GLOBAL) n = snprintf(buf, len, "conv_mfma_kernel<%d, %d, %d, %d, %s>", p.bm, p.bn, p.wm, p.wn, tf);
+    else n = snprintf(buf, len, "conv_mfma_buf_kernel%s<%d, %d, %d, %d, %d, %s>", CONV_TAG[m], p.bm, p.bn, p.wm, p.wn, p.cch, tf);
+    PCC_REQUIRE(n < len, "pcc_conv_kernel_name: %d bytes do not hold the name", len);
+    return PCC_OK;
 }
 
 }  // extern "C"

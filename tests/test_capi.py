@@ -95,3 +95,67 @@ def test_build_checks_of_the_convolution_kernels(pcc):
     import pytest
     with pytest.raises(RuntimeError, match="still in flight"):
         _lib.lint_lds_reads(bad)
+
+
+# (cin, cout, n_out, has_nbr) -> the kernel pcc_conv_fwd launches (K = 27 with a map, else 1 and n_in = n_out)
+_FP32_PLANS = [
+    (128, 128, 1_000, True, "conv_small_kernel<4, 3>"),
+    (64, 64, 5_000, True, "conv_small_kernel<2, 3>"),
+    (96, 32, 3_000, True, "conv_small_kernel<1, 8>"),
+    (128, 128, 30_000, True, "conv_mfma_buf_kernel<64, 64, 2, 2, 4, true>"),
+    (96, 128, 20_000, True, "conv_mfma_buf_kernel<64, 64, 2, 2, 3, true>"),
+    (128, 128, 72_000, True, "conv_mfma_buf_kernel<32, 128, 1, 4, 4, true>"),
+    (128, 128, 1_263_766, True, "conv_mfma_buf_kernel<64, 128, 2, 2, 4, true>"),
+    (64, 64, 5_160_000, True, "conv_mfma_buf_kernel<128, 64, 2, 2, 2, true>"),
+    (32, 32, 200_000, True, "conv_mfma_buf_kernel<128, 32, 4, 1, 1, true>"),
+    (128, 128, 100_000, False, "conv_mfma_buf_kernel<32, 128, 1, 4, 4, false>"),
+    (3, 8, 50_000, True, "conv_thin_kernel<3, 8>"),
+    (2, 6, 700, True, "conv_thin_kernel<2, 2>"),
+]
+
+
+def test_conv_kernel_name_follows_the_launch_plan(pcc):
+    """pcc_conv_kernel_name: the kernel and template parameters each mode's launch runs (csrc/conv.hip, plan_conv), on the host"""
+    import ctypes
+    L = pcc.lib()
+
+    def name(mode, cin, cout, n_out, has_nbr=True, n_in=None, K=None):
+        buf = ctypes.create_string_buffer(128)
+        rc = L.pcc_conv_kernel_name(mode, n_out if n_in is None else n_in, cin, cout, n_out, (27 if has_nbr else 1) if K is None else K,
+                                    int(has_nbr), buf, len(buf))
+        return buf.value.decode() if rc == 0 else rc
+
+    for cin, cout, n_out, has_nbr, want in _FP32_PLANS:
+        assert name(0, cin, cout, n_out, has_nbr) == want, (cin, cout, n_out, has_nbr)
+    # bf16: chunks of 64 channels, never the small kernel; x3: 64 x 64 tiles for 64-wide outputs, nothing for 32-wide ones
+    assert name(1, 128, 128, 1_000) == "conv_mfma_buf_kernel[bf16]<64, 64, 2, 2, 2, true>"
+    assert name(1, 128, 128, 1_263_766) == "conv_mfma_buf_kernel[bf16]<64, 128, 2, 2, 2, true>"
+    assert name(1, 256, 64, 5_160_000) == "conv_mfma_buf_kernel[bf16]<128, 64, 2, 2, 4, true>"
+    assert name(1, 64, 32, 200_000) == "conv_mfma_buf_kernel[bf16]<128, 32, 4, 1, 1, true>"
+    assert name(1, 128, 128, 72_000, has_nbr=False) == "conv_mfma_buf_kernel[bf16]<64, 128, 2, 2, 2, false>"
+    assert name(2, 128, 128, 1_000) == "conv_mfma_buf_kernel[x3]<64, 64, 2, 2, 4, true>"
+    assert name(2, 128, 128, 72_000) == "conv_mfma_buf_kernel[x3]<64, 128, 2, 2, 4, true>"
+    assert name(2, 64, 64, 5_160_000) == "conv_mfma_buf_kernel[x3]<64, 64, 2, 2, 2, true>"
+    assert name(2, 96, 64, 5_000) == "conv_mfma_buf_kernel[x3]<64, 64, 2, 2, 3, true>"
+    unsupported = -3                                                # PCC_ERR_UNSUPPORTED
+    for mode, cin, cout in ((2, 64, 32), (2, 64, 96), (1, 96, 128), (1, 3, 8), (2, 3, 8), (1, 512, 128), (0, 5, 8), (0, 288, 64)):
+        assert name(mode, cin, cout, 10_000) == unsupported, (mode, cin, cout)
+    # operands past the 32-bit buffer offsets: the 64-bit-addressed kernel in fp32, nothing in bf16 / x3
+    assert name(0, 128, 64, 9_000_000) == "conv_mfma_kernel<128, 64, 2, 2, true>"
+    assert name(0, 128, 128, 9_000_000, has_nbr=False) == "conv_mfma_kernel<64, 128, 2, 2, false>"
+    assert name(0, 128, 128, 500, n_in=9_000_000) == "conv_mfma_kernel<64, 64, 2, 2, true>"
+    assert name(1, 256, 128, 9_000_000) == unsupported and name(2, 128, 128, 9_000_000) == unsupported
+    assert name(1, 128, 128, 45_000_000, n_in=1_000_000) == unsupported      # the map alone: n_out * K * 4 bytes
+    assert name(0, 128, 128, 10_000, has_nbr=False, n_in=5_000) < 0    # no map: one row per input row
+    # the small-kernel threshold is host state the plan reads
+    was = L.pcc_conv_small_max(0)
+    try:
+        assert name(0, 128, 128, 1_000) == "conv_mfma_buf_kernel<64, 64, 2, 2, 4, true>"
+        L.pcc_conv_small_max(64)
+        assert name(0, 128, 128, 500) == "conv_small_kernel<4, 3>" and name(0, 128, 128, 600).startswith("conv_mfma_buf_kernel")
+        assert name(0, 64, 64, 1_000) == "conv_small_kernel<2, 3>"          # 32 x 32 tiles x 2 for outputs below 128 wide
+    finally:
+        L.pcc_conv_small_max(was)
+    assert name(0, 128, 128, 1_000) == "conv_small_kernel<4, 3>"
+    # a buffer too short for the name is an argument error, not a truncated name
+    assert L.pcc_conv_kernel_name(0, 1000, 128, 128, 1000, 27, 1, ctypes.create_string_buffer(8), 8) == -1

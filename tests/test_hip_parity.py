@@ -622,53 +622,46 @@ def test_gaussian_conditional_packed_planes(pcc, oracle_codec):
         assert torch.equal(back, want)
 
 
-_THIN_SCRIPT = r"""
-import hashlib, sys
-import numpy as np, torch
-sys.path.insert(0, {root!r})
-import pcc_amd
-from pcc_amd import sparse as sp
-torch.manual_seed(5)
-torch.set_grad_enabled(False)          # the inference kernels (with gradients on, trainable layers take the autograd path)
-rng = np.random.default_rng(2)
-p = pcc_amd.synthetic.sphere_shell(64, 27.0, 0.9)[:, :3]
-c = np.concatenate([np.zeros((p.shape[0], 1)), p], axis=1).astype(np.int32)
-c = c[rng.permutation(c.shape[0])]
-sub = c[rng.random(c.shape[0]) < 0.4]
-h = hashlib.sha256()
-for coords in (c, sub, c[:70], c[:1]):
-    n = coords.shape[0]
-    m = pcc_amd.CoordMap(torch.from_numpy(coords).cuda(), 1)
-    for cin, cout in ((2, 128), (4, 64), (2, 64), (16, 32), (1, 32), (8, 64), (4, 96)):
-        layer = pcc_amd.MinkowskiConvolution(cin, cout, kernel_size=3, stride=1, bias=True, dimension=3).cuda()
-        x = pcc_amd.SparseTensor(torch.randn(n, cin).cuda(), coordinate_map=m)
-        film, res = torch.randn(n, 2 * cout).cuda(), torch.randn(n, cout).cuda()
-        for kw in ({{}}, dict(act=sp.ACT_RELU, residual=res), dict(act=sp.ACT_LRELU, film=film, residual=res)):
-            h.update(layer(x, **kw).F.cpu().numpy().tobytes())
-    # strided and transposed maps (K = 27 and K = 8) with thin inputs
-    m2 = pcc_amd.CoordMap(torch.from_numpy(coords * np.array([1, 2, 2, 2], np.int32)).cuda(), 2)
-    x2 = pcc_amd.SparseTensor(torch.randn(n, 2).cuda(), coordinate_map=m2)
-    for layer in (pcc_amd.MinkowskiConvolution(2, 64, kernel_size=3, stride=2, bias=True, dimension=3),
-                  pcc_amd.MinkowskiGenerativeConvolutionTranspose(2, 32, kernel_size=2, stride=2, bias=True, dimension=3),
-                  pcc_amd.MinkowskiGenerativeConvolutionTranspose(2, 64, kernel_size=3, stride=2, bias=True, dimension=3)):
-        h.update(layer.cuda()(x2).F.cpu().numpy().tobytes())
-print("DIGEST", h.hexdigest())
-"""
-
-
-def test_thin_im2col_mfma_equals_thin_kernel_bitwise():
+def test_thin_im2col_mfma_equals_thin_kernel_bitwise(pcc):
     """thin inputs, wide outputs (2 -> 128, 4 -> 64, ...): im2col + one kernel_size-1 MFMA convolution (the default) against the
-    scalar conv_thin_kernel (PCC_THIN_IM2COL=0): the fp32 MFMA is the same fused multiply-add chain as v_fma_f32 and the matrix
-    columns are laid out in the order the MFMA loop contracts them, so the same bits — over dense / sparse / 70-row / one-row
-    sets, every epilogue, strided and transposed maps"""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    digests = []
-    for flag in ("1", "0"):
-        env = dict(os.environ, PCC_THIN_IM2COL=flag)
-        r = subprocess.run([sys.executable, "-c", _THIN_SCRIPT.format(root=root)], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        digests.append([ln for ln in r.stdout.splitlines() if ln.startswith("DIGEST")][0])
-    assert digests[0] == digests[1]
+    scalar conv_thin_kernel (pcc_conv_fwd on the layer's raw weights, cin < 32): the fp32 MFMA is the same fused multiply-add
+    chain as v_fma_f32 and the matrix columns are laid out in the order the MFMA loop contracts them, so the same bits — over
+    dense / sparse / 70-row / one-row sets, every epilogue, strided and transposed maps"""
+    from pcc_amd import sparse as sp
+    from pcc_amd._lib import check, lib, ptr, stream
+    L = lib()
+    torch.manual_seed(5)
+    rng = np.random.default_rng(2)
+    p = pcc.synthetic.sphere_shell(64, 27.0, 0.9)[:, :3]
+    c = np.concatenate([np.zeros((p.shape[0], 1)), p], axis=1).astype(np.int32)
+    c = c[rng.permutation(c.shape[0])]
+    sub = c[rng.random(c.shape[0]) < 0.4]
+
+    def same_as_thin_kernel(layer, x, act=sp.ACT_NONE, film=None, residual=None):
+        out_map = layer.output_map(x.map)
+        with torch.no_grad():
+            got = layer(x, act=act, film=film, residual=residual, out_map=out_map).F
+        nbr, _, _ = x.map.kernel_map(out_map, layer.kernel_size, layer.transposed)
+        w, _, b = layer.weights()
+        want = torch.empty_like(got)
+        check(L.pcc_conv_fwd(ptr(x.F), x.F.shape[0], x.F.shape[1], ptr(w), None, ptr(b), ptr(nbr), None, None, nbr.shape[1], ptr(want),
+                             out_map.n, w.shape[2], act, ptr(film), ptr(residual), stream()))
+        assert torch.equal(got, want), (x.F.shape, w.shape, act)
+
+    for coords in (c, sub, c[:70], c[:1]):
+        n = coords.shape[0]
+        m = pcc.CoordMap(torch.from_numpy(coords).to(DEV), 1)
+        for cin, cout in ((2, 128), (4, 64), (2, 64), (16, 32), (1, 32), (8, 64), (4, 96)):
+            layer = pcc.MinkowskiConvolution(cin, cout, kernel_size=3, stride=1, bias=True, dimension=3).to(DEV)
+            x = pcc.SparseTensor(torch.randn(n, cin).to(DEV), coordinate_map=m)
+            film, res = torch.randn(n, 2 * cout).to(DEV), torch.randn(n, cout).to(DEV)
+            for kw in ({}, dict(act=sp.ACT_RELU, residual=res), dict(act=sp.ACT_LRELU, film=film, residual=res)):
+                same_as_thin_kernel(layer, x, **kw)
+    # strided and transposed maps (K = 27 and K = 8) with thin inputs
+    for coords in (c, c[:1]):
+        m2 = pcc.CoordMap(torch.from_numpy(coords * np.array([1, 2, 2, 2], np.int32)).to(DEV), 2)
+        x2 = pcc.SparseTensor(torch.randn(coords.shape[0], 2).to(DEV), coordinate_map=m2)
+        for layer in (pcc.MinkowskiConvolution(2, 64, kernel_size=3, stride=2, bias=True, dimension=3),
+                      pcc.MinkowskiGenerativeConvolutionTranspose(2, 32, kernel_size=2, stride=2, bias=True, dimension=3),
+                      pcc.MinkowskiGenerativeConvolutionTranspose(2, 64, kernel_size=3, stride=2, bias=True, dimension=3)):
+            same_as_thin_kernel(layer.to(DEV), x2)
