@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: ColorModel.compress + decompress of one 10-bit frame per step.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--full]
+  A plain run does what the headline figure needs and no more: set-up, W warm-up steps, K timed steps, the files of
+  --dump-outputs, the result line (`value`, `ms_per_step`, the roofline of the dominant convolution class from the events of
+  the timed steps, replayed committed figures beside it, labelled).  --full adds everything that takes runs of its own: the
+  CPU baseline with its parity check, the `blocks`, `split_bf16`, `small_frame`, `streamed`, `roofline_hbm`, `mid_frame` and
+  `train_step` records and the rocprofv3 --pmc child passes (about two minutes on top; each has its --no-... switch).
   N > 1: one rank per GPU over RCCL.  Either the driver starts the ranks (python -m torch.distributed.run ...
   bench.py --gpus N: RANK / WORLD_SIZE are in the environment) or bench.py does it itself: with --gpus N > 1 and no
   RANK it starts `python -m torch.distributed.run --nproc-per-node N bench.py <same arguments>` as a CHILD process,
@@ -69,6 +74,11 @@ def kernel_source_sha256():
 
 LIVE_PMC_FLAGS = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-blocks-record", "--no-x3-record", "--no-streamed-record",
                   "--no-small-frame-record", "--no-mid-frame-record", "--no-train-record", "--no-hbm-record", "--no-live-pmc"]
+
+
+# the records of a --full run, by the switch that turns each off: a run without --full has all of them set
+FULL_ONLY = ("no_cpu_baseline", "no_blocks_record", "no_x3_record", "no_streamed_record", "no_small_frame_record",
+             "no_mid_frame_record", "no_train_record", "no_hbm_record", "no_live_pmc")
 
 
 def live_traffic(kernel_substr, timeout_s=150):
@@ -305,7 +315,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="config2", choices=["config1", "config2", "mid"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what is not the headline figure: the CPU baseline and its parity check, "
+                         "the blocks / split_bf16 / small_frame / streamed / roofline_hbm / mid_frame / train_step records and "
+                         "roofline.traffic by rocprofv3 --pmc child passes (about two minutes more).  Without it none of them runs "
+                         "and the --no-... switches below, --cpu-order and --cpu-sample have nothing to act on")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the `cpu_baseline` record of a --full run")
     ap.add_argument("--cpu-order", default="kernel", choices=["kernel", "blas"],
                     help="summation order of the CPU baseline's oracle: kernel = hand-vectorised fused multiply-add chains (the faster CPU "
                          "implementation, ~45 s on the config-2 frame; the HIP path must reproduce its bytes), blas = torch-CPU sgemm (~130 s)")
@@ -320,7 +335,7 @@ def parse():
     ap.add_argument("--block", type=int, default=512, help="cube edge of --partition blocks")
     ap.add_argument("--no-blocks-record", action="store_true",
                     help="skip the strong-scaling 'blocks' sub-record (one frame cut into cubes over the ranks) that "
-                         "a frames run reports beside its value")
+                         "a --full frames run reports beside its value")
     ap.add_argument("--weights", default=None,
                     help="state_dict to load instead of the seeded initialisation (e.g. from tools/train.py); the headline "
                          "configuration is the seeded one")
@@ -329,16 +344,16 @@ def parse():
                          "headline configuration — the reference computes in fp32 and so does the default run")
     ap.add_argument("--x3", action="store_true",
                     help="opt-in split-bf16 arithmetic (fp32 data, three-way bf16 split of both operands, six bf16 MFMA products with "
-                         "fp32 accumulation) on the wide convolutions for the WHOLE run; NOT the headline configuration — a default "
+                         "fp32 accumulation) on the wide convolutions for the WHOLE run; NOT the headline configuration — a --full "
                          "run reports this mode as the `split_bf16` sub-record beside the fp32 value")
-    ap.add_argument("--no-x3-record", action="store_true", help="skip the `split_bf16` sub-record of a default run")
-    ap.add_argument("--no-streamed-record", action="store_true", help="skip the `streamed` sub-record of a default run")
-    ap.add_argument("--no-small-frame-record", action="store_true", help="skip the `small_frame` sub-record of a default run")
-    ap.add_argument("--no-mid-frame-record", action="store_true", help="skip the `mid_frame` sub-record of a default run")
-    ap.add_argument("--no-train-record", action="store_true", help="skip the `train_step` sub-record of a default run")
-    ap.add_argument("--no-hbm-record", action="store_true", help="skip the `roofline_hbm` record of a default run")
+    ap.add_argument("--no-x3-record", action="store_true", help="skip the `split_bf16` sub-record of a --full run")
+    ap.add_argument("--no-streamed-record", action="store_true", help="skip the `streamed` sub-record of a --full run")
+    ap.add_argument("--no-small-frame-record", action="store_true", help="skip the `small_frame` sub-record of a --full run")
+    ap.add_argument("--no-mid-frame-record", action="store_true", help="skip the `mid_frame` sub-record of a --full run")
+    ap.add_argument("--no-train-record", action="store_true", help="skip the `train_step` sub-record of a --full run")
+    ap.add_argument("--no-hbm-record", action="store_true", help="skip the `roofline_hbm` record of a --full run")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not measure roofline.traffic in this run (two rocprofv3 --pmc child passes, ~40 s): replay the committed figure")
+                    help="do not measure roofline.traffic in a --full run (two rocprofv3 --pmc child passes, ~40 s): replay the committed figure")
     ap.add_argument("--file-mode", action="store_true",
                     help="after the timed region, also time compress(path=...) / decompress(path=...) (t_file, SURVEY.md 8d)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -348,6 +363,10 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run: the timed steps and what is derived from them; every record that runs steps, passes or processes of its own is off
+        for name in FULL_ONLY:
+            setattr(args, name, True)
     return args
 
 
@@ -1057,7 +1076,7 @@ def main():
                            "kernel_source_unchanged_since": tj.get("kernel_source_sha256") == kernel_source_sha256(),
                            "how": "separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, FETCH x2 gfx950 "
                                   "correction (tools/pmc_traffic.py); replayed from the committed file, not measured in this run"}
-        # ... unless it can be measured here and now (default N = 1 run): the same two passes as children of this process
+        # ... unless it can be measured here and now (--full N = 1 run): the same two passes as children of this process
         if (traffic_src is not None and rank == 0 and world == 1 and not args.no_live_pmc and not args.bf16 and not args.x3
                 and not blocks_mode and not args.weights and os.environ.get("PCC_BENCH_MARK") != "1"):
             print("[bench] roofline.traffic: two rocprofv3 --pmc child passes ...", file=sys.stderr, flush=True)
@@ -1257,8 +1276,8 @@ def main():
         sd = {n_: t.detach().cpu() for n_, t in model.state_dict().items()}
         out["cpu_baseline"] = cpu_baseline(model, sd, args.cpu_sample, dev, args.cpu_order)
         if args.cpu_order == "kernel":
-            # the slower CPU implementation SURVEY.md §8d names (torch-CPU sgemm per offset + index_add_) is not re-run by the default
-            # command (2.5 minutes); its newest committed measurement (`python bench.py --cpu-order blas`) rides along, labelled
+            # the slower CPU implementation SURVEY.md §8d names (torch-CPU sgemm per offset + index_add_) is not re-run by a --full
+            # run (2.5 minutes); its newest committed measurement (`python bench.py --full --cpu-order blas`) rides along, labelled
             other = latest_profile("cpu_baseline_blas_order")
             if other and other.get("cpu_baseline"):
                 ob = other["cpu_baseline"]
@@ -1267,7 +1286,7 @@ def main():
                     "parity_abs_diff": ob.get("parity", {}).get("abs_diff"), "decoded_voxels_differing": ob.get("parity", {}).get("decoded_voxels_differing"),
                     "replayed_from": {"file": other["_file"], "commit": other.get("commit"), "note": "not re-measured in this run"}}
     elif rank == 0:
-        # N > 1 (and --no-cpu-baseline): the baseline is measured on rank 0 at N = 1 only (minutes of host work); carry the newest
+        # N > 1, a plain run, --no-cpu-baseline: the baseline is measured on rank 0 of a --full N = 1 run only (minutes of host work); carry the newest
         # committed N = 1 record along, labelled as replayed, so that a scaling line is as complete as the N = 1 line
         prev = latest_profile("bench_config2")
         cb = (prev or {}).get("cpu_baseline")

@@ -142,3 +142,19 @@ def test_dump_outputs_arrays_budget_and_files(tmp_path):
 def test_bench_refuses_zero_steps():
     r = _bench(["--steps", "0"], {})
     assert r.returncode != 0 and "--steps must be at least 1" in r.stderr and not r.stdout.strip()
+
+
+def test_a_plain_run_has_every_extra_record_off_and_full_brings_them_back(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` measures the headline figure alone: every record that takes steps, profiler passes
+    or child processes of its own belongs to --full, where each keeps its own --no-... switch"""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    plain = bench.parse()
+    assert not plain.full and all(getattr(plain, name) for name in bench.FULL_ONLY)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-train-record"])
+    full = bench.parse()
+    assert full.full and [name for name in bench.FULL_ONLY if getattr(full, name)] == ["no_train_record"]
+    assert (full.steps, full.warmup, full.dump_outputs) == (plain.steps, plain.warmup, plain.dump_outputs) == (3, 1, None)
+    # every switch of that kind is in the list: the profiler's child passes of this command name the same ones
+    assert {n for n in vars(plain) if n.startswith("no_")} == set(bench.FULL_ONLY)
+    assert {"--" + name.replace("_", "-") for name in bench.FULL_ONLY} <= set(bench.LIVE_PMC_FLAGS)

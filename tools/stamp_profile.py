@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Copy a bench.py result line (gpurun_out/*.json) into profiles/ with the commit and kernel-source hash it was taken at.
+"""Copy a `bench.py --full` result line (a file holding it) into profiles/ with the commit and kernel-source hash it was taken at.
 
-usage: stamp_profile.py <gpurun_out/line.json> <profiles/rNN_name.json> [commit]
-Run in the build container right after the GPU call, before the sources move on (bench.py replays cpu_baseline of the newest
-profiles/rNN_bench_config2.json at N > 1 and names this commit)."""
+usage: stamp_profile.py <line.json> <profiles/rNN_name.json> [commit]
+Run right after the GPU job, before the sources move on (bench.py replays cpu_baseline of the newest
+profiles/rNN_bench_config2.json in plain runs and at N > 1, and names this commit: the line must come from a --full run, whose
+cpu_baseline is measured, not from a plain one, whose cpu_baseline is itself a replay)."""
 import json
 import os
 import subprocess
