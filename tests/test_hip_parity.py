@@ -212,6 +212,10 @@ def test_kernel_map(pcc, case):
             assert (np.diff(order_key(want_mask)[order]) >= 0).all()
 
 
+# What test_conv_forward_matches_oracle reaches with these at its ~5 k-row shell and the default small-launch threshold: the
+# small-launch kernel for every cin % 32 == 0 shape (kernel_size 3) except cout = 256 (64 x 64 tile); 64 x 64 without a map for
+# (128, 128, 1); the narrow-head path for cout <= 4 on wide inputs; the thin kernels (or im2col and a map-less tile) for the
+# rest.  The other tiles, chunk counts and the large-launch plans are compared per launch in tests/test_conv_plans.py.
 CONV_SHAPES = [
     # cin, cout, ksize  (every (C_in, C_out) pair of configs/Ours.yaml)
     (128, 128, 3), (64, 128, 3), (128, 256, 3), (128, 64, 3), (64, 64, 3), (64, 32, 3), (32, 3, 3),
