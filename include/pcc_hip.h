@@ -422,6 +422,52 @@ int pcc_rans_decode_with_indexes_u8i16(const uint8_t* data, int64_t nbytes, cons
 /* cdf has n+1 entries. */
 int pcc_pmf_to_quantized_cdf(const float* pmf, int32_t n, int32_t precision, int32_t* cdf);
 
+/* ---------------------------------------------------------------------------------------
+ * The lane-parallel y stream "PCL1" (opt-in).  The symbol sequence is dealt to
+ * `lanes` lanes (lane s owns positions s, s + lanes, ...) and lane s's substream is exactly
+ * what pcc_rans_encode_with_indexes writes for that subsequence alone.  Container, little-
+ * endian: "PCL1", lanes (uint16, 1 .. 4096), uint16 0, lanes x uint32 byte length (0, or a
+ * multiple of 4 that is >= 8), then the substreams in lane order.
+ * ------------------------------------------------------------------------------------- */
+/* Checks a container's header (magic, lane count, length rules, lengths add up to nbytes):
+ * the lane count, or PCC_ERR_DATA.  HOST pointer. */
+int64_t pcc_rans_lanes_header(const uint8_t* data, int64_t nbytes);
+/* Host twin of the GPU coder; all pointers HOST.  Encode returns the bytes written
+ * (<= 8 + 4*lanes + 8*n + 16*lanes); decode checks the header, that every lane ends at state
+ * 2^31 and at the end of its substream (PCC_ERR_DATA otherwise), and never reads outside data. */
+int64_t pcc_rans_lanes_encode_host(const int32_t* symbols, const int32_t* indexes, int64_t n, int32_t lanes,
+                                   const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
+                                   const int32_t* offsets, uint8_t* out, int64_t out_cap);
+int pcc_rans_lanes_decode_host(const uint8_t* data, int64_t nbytes, const int32_t* indexes, int64_t n,
+                               const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
+                               const int32_t* offsets, int32_t* out_symbols);
+/* The coding tables of the kernels below, built on the HOST into `out` (pcc_rans_lanes_tables_bytes
+ * of it; n_tables <= 256); the caller copies the blob to 16-byte aligned device memory and keeps
+ * it while the tables stand. */
+int64_t pcc_rans_lanes_tables_bytes(const int32_t* cdf_sizes, int32_t n_tables);
+int pcc_rans_lanes_tables_build(const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
+                                const int32_t* offsets, int32_t n_tables, void* out, int64_t out_bytes);
+/* GPU encoder: symbols / indexes are DEVICE int32 sequences of n < 2^27 in stream order, `tables`
+ * the device copy of the blob.  Writes the container to `out` (device, 4-byte aligned,
+ * pcc_rans_lanes_encode_out_bytes of it) and result[0] = its size in bytes, result[1] = flags
+ * (device int32[2]): bit 0 = a lane outgrew its share of the scratch, nothing was written past
+ * it and `out` is unusable: repeat the call with worst_case = 1 (the first-guess scratch holds
+ * 2 bytes per symbol); bit 1 = table index out of range, bit 2 = symbol of frequency 0, bit 3 =
+ * `tables` is not a table blob.  scratch: device, pcc_rans_lanes_encode_scratch_bytes of it. */
+int64_t pcc_rans_lanes_encode_scratch_bytes(int64_t n, int32_t lanes, int32_t worst_case);
+int64_t pcc_rans_lanes_encode_out_bytes(int64_t n, int32_t lanes, int32_t worst_case);
+int pcc_rans_lanes_encode(const int32_t* symbols, const int32_t* indexes, int64_t n, int32_t lanes,
+                          const void* tables, int32_t worst_case, void* scratch, int64_t scratch_bytes,
+                          uint8_t* out, int64_t out_cap, int32_t* result, void* stream);
+/* GPU decoder: `data_host` and `data` are the HOST and the DEVICE (4-byte aligned) copy of one
+ * container of nbytes; the header is checked on the host copy before anything is launched
+ * (PCC_ERR_DATA).  indexes: device int32 [n]; out_symbols: device int32 [n] (the [C, N] plane
+ * pcc_gc_dequantize reads).  *status (device int32) is 0 after a clean decode; bit 4 = a lane did
+ * not end at state 2^31 and the end of its substream, bits 1 and 3 as above.  Reads of the stream
+ * are clamped to each lane's substream. */
+int pcc_rans_lanes_decode(const uint8_t* data_host, const uint8_t* data, int64_t nbytes, const int32_t* indexes,
+                          int64_t n, const void* tables, int32_t* out_symbols, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,15 @@ SIGNATURES = {
     "pcc_rans_encode_with_indexes": (c_i64, [c_void_p, c_void_p, c_i64, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_i64]),
     "pcc_rans_decode_with_indexes": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_void_p, c_void_p, c_void_p]),
     "pcc_pmf_to_quantized_cdf": (c_int, [c_void_p, c_i32, c_i32, c_void_p]),
+    "pcc_rans_lanes_header": (c_i64, [c_void_p, c_i64]),
+    "pcc_rans_lanes_encode_host": (c_i64, [c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_i64]),
+    "pcc_rans_lanes_decode_host": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_void_p, c_void_p, c_void_p]),
+    "pcc_rans_lanes_tables_bytes": (c_i64, [c_void_p, c_i32]),
+    "pcc_rans_lanes_tables_build": (c_int, [c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_i64]),
+    "pcc_rans_lanes_encode_scratch_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "pcc_rans_lanes_encode_out_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "pcc_rans_lanes_encode": (c_int, [c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p]),
+    "pcc_rans_lanes_decode": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 
@@ -99,6 +108,7 @@ def build(force=False):
         subprocess.check_call(args + ["clean"])
     subprocess.check_call(args)
     check_kernel_resources()
+    check_kernel_resources(os.path.join(_HERE, "build", "rans_lanes.resources.txt"), LANE_KERNELS)
     check_small_kernel_lds_reads()
     return SO_PATH
 
@@ -107,6 +117,9 @@ def build(force=False):
 # conv_small_kernel's inline-assembly LDS reads sit behind a hand-placed s_waitcnt that the compiler does not see: a spilled
 # or copied operand register would be read before its data has landed, silently)
 NO_SCRATCH_KERNELS = ("conv_small_kernel", "conv_mfma_buf_kernel", "conv_mfma_kernel")
+# the lane-parallel range coder (csrc/rans_lanes.hip): one thread carries one serial state chain, and a spilled state or
+# batch register would put a scratch round trip into every link of it
+LANE_KERNELS = ("rans_lanes_encode_kernel", "rans_lanes_pack_kernel", "rans_lanes_decode_kernel")
 
 
 def check_small_kernel_lds_reads(obj=None):
@@ -185,10 +198,12 @@ def lint_lds_reads(dis, kernel="conv_small_kernel"):
     return checked
 
 
-def check_kernel_resources(path=None):
+def check_kernel_resources(path=None, kernels=None):
     """Parse the compiler's per-kernel resource remarks (csrc/Makefile writes them beside the objects) and fail loudly
-    when one of NO_SCRATCH_KERNELS uses scratch memory or spills registers.  -> {mangled kernel name: (vgprs, scratch)}"""
+    when one of ``kernels`` (default NO_SCRATCH_KERNELS) uses scratch memory or spills registers.
+    -> {mangled kernel name: (vgprs, scratch)}"""
     import re
+    NO_SCRATCH_KERNELS = kernels or globals()["NO_SCRATCH_KERNELS"]
     path = path or os.path.join(_HERE, "build", "conv.resources.txt")
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: the library was not built by csrc/Makefile")

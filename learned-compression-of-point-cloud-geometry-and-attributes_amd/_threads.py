@@ -98,6 +98,8 @@ class _State:
         self.pinned = {}            # name -> page-locked staging buffer (entropy.py)
         self.pin_busy = {}          # name -> event behind the last asynchronous upload from that buffer
         self.count = None           # (page-locked int64 tensor, numpy view of it): the row-count word (sparse.py)
+        self.lane_buffers = {}      # (name, device) -> device scratch / stream buffer of the lane-parallel y coder (entropy.py)
+        self.lane_status = []       # device status words of the lane-parallel y decodes not yet checked (entropy.py)
         # when the owning thread ends; not at exit, where the job threads of the threads still alive stay parked
         weakref.finalize(self, _close_all, self._job_threads).atexit = False
 

@@ -11,6 +11,7 @@ ops, compressai's LowerBound gradients — is ``forward(..., training=True)`` / 
 """
 import functools
 import math
+import os
 
 import numpy as np
 import scipy.stats
@@ -196,6 +197,91 @@ def _rans_decode(data, indexes, cdf, cdf_length, offset):
     return out
 
 
+# ---- the lane-parallel y stream ("PCL1") --------------------------------------------------------------
+# Opt-in stream format of the y string: the symbol sequence dealt to STREAM_LANES lanes, each lane's substream what the
+# reference-format coder writes for its symbols alone, coded and decoded by one GPU thread per lane (csrc/rans_lanes.hip) —
+# only the stream bytes cross PCIe, and no host range coder sits between the GPU work of a frame.  0 (the default) is the
+# reference's format, byte for byte.  The z string is in the reference's format in every mode.  The decoder takes the lane
+# count from the stream, so any encoder's count decodes, but encoder and decoder must agree on the FORMAT: with lanes set, a
+# y string without the magic is refused.  PCC_STREAM_LANES=n / set_stream_lanes(n).
+LANES_MAGIC = b"PCL1"
+LANES_MAX = 4096
+
+
+def _lanes_setting(n):
+    n = int(n)
+    if not 0 <= n <= LANES_MAX:
+        raise ValueError(f"PCC_STREAM_LANES / set_stream_lanes: {n} lanes (0 = the reference's format, or 1 .. {LANES_MAX})")
+    return n
+
+
+STREAM_LANES = _lanes_setting(os.environ.get("PCC_STREAM_LANES", "0") or 0)
+LANES_RETRIES = 0          # encodes repeated with the worst-case scratch (a counter for tests and profiles)
+
+
+def set_stream_lanes(n):
+    global STREAM_LANES
+    STREAM_LANES = _lanes_setting(n)
+
+
+def _rans_lanes_encode_host(symbols, indexes, lanes, cdf, cdf_length, offset):
+    """host twin of the GPU encoder: int32 host arrays -> PCL1 bytes"""
+    L = _lib.lib()
+    symbols = np.ascontiguousarray(symbols, dtype=np.int32).reshape(-1)
+    indexes = np.ascontiguousarray(indexes, dtype=np.int32).reshape(-1)
+    n = symbols.size
+    head = 8 + 4 * int(lanes)
+    for cap in (head + n + 4096 + 16 * int(lanes), head + 8 * n + 16 * int(lanes) + 16):
+        out = np.empty(cap, dtype=np.uint8)
+        nbytes = L.pcc_rans_lanes_encode_host(ptr(symbols), ptr(indexes), n, int(lanes), ptr(cdf), cdf.shape[1], ptr(cdf_length),
+                                              ptr(offset), ptr(out), cap)
+        if nbytes >= 0:
+            return out[:nbytes].tobytes()
+    check(nbytes)
+
+
+def _rans_lanes_decode_host(data, indexes, cdf, cdf_length, offset):
+    """host twin of the GPU decoder: PCL1 bytes -> int32 symbols; a malformed or corrupt stream raises"""
+    L = _lib.lib()
+    indexes = np.ascontiguousarray(indexes, dtype=np.int32).reshape(-1)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    out = np.empty(indexes.size, dtype=np.int32)
+    check(L.pcc_rans_lanes_decode_host(ptr(buf), len(data), ptr(indexes), indexes.size, ptr(cdf), cdf.shape[1], ptr(cdf_length),
+                                       ptr(offset), ptr(out)))
+    return out
+
+
+def _lane_buffer(key, nbytes, device):
+    """The calling thread's device buffer ``key`` of the lane coder (grown, never shrunk): two frames in flight on two coding
+    threads do not share scratch; the frames of one thread follow each other on its stream."""
+    bufs = _threads.current().lane_buffers
+    buf = bufs.get((key, device))
+    if buf is None or buf.numel() < nbytes:
+        buf = bufs[(key, device)] = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+    return buf
+
+
+_LANE_FLAGS = ((1, "a lane outgrew its scratch"), (2, "table index out of range"), (4, "symbol of frequency 0"),
+               (8, "not a table blob"), (16, "a lane did not end at its initial state and the end of its substream"))
+
+
+def _lane_flag_text(bits):
+    return ", ".join(text for bit, text in _LANE_FLAGS if bits & bit) or "unknown"
+
+
+def check_stream_status():
+    """The status words of the calling thread's lane-parallel y decodes since the last call, read once (ColorModel.decompress
+    calls this after g_s is enqueued: the decode itself never waits for the host).  A non-zero word raises ValueError."""
+    st = _threads.current()
+    pending, st.lane_status = st.lane_status, []
+    bits = 0
+    for word in pending:
+        bits |= int(word.item())
+    if bits:
+        raise ValueError(f"lane-parallel y stream (PCC_STREAM_LANES): the decoder reports status {bits:#x} ({_lane_flag_text(bits)}): "
+                         "the stream is corrupt or was coded with other tables")
+
+
 class _EntropyModelBase(nn.Module):
     def __init__(self, likelihood_bound=1e-9, entropy_coder_precision=16):
         super().__init__()
@@ -212,6 +298,22 @@ class _EntropyModelBase(nn.Module):
         self._cdf_length = torch.from_numpy(cdf_length).to(dev)
         self._offset = torch.from_numpy(offset).to(dev)
         self._host_tables = (np.ascontiguousarray(cdf), np.ascontiguousarray(cdf_length), np.ascontiguousarray(offset))
+        self.__dict__["_lane_tables"] = {}
+
+    def lane_tables(self, device):
+        """The coding tables of the lane-parallel coder on ``device`` (pcc_rans_lanes_tables_build): built at the first use after
+        update() / a checkpoint load and kept there."""
+        cache = self.__dict__.setdefault("_lane_tables", {})
+        device = torch.device(device)
+        blob = cache.get(device)
+        if blob is None:
+            cdf, cdf_len, off = self.tables()
+            L = _lib.lib()
+            nbytes = check(L.pcc_rans_lanes_tables_bytes(ptr(cdf_len), cdf_len.size))
+            host = np.empty(nbytes, dtype=np.uint8)
+            check(L.pcc_rans_lanes_tables_build(ptr(cdf), cdf.shape[1], ptr(cdf_len), ptr(off), cdf_len.size, ptr(host), nbytes))
+            blob = cache[device] = torch.from_numpy(host).to(device)
+        return blob
 
     def tables(self):
         if self._host_tables is None:
@@ -230,6 +332,7 @@ class _EntropyModelBase(nn.Module):
             if key in state_dict and hasattr(self, name):
                 setattr(self, name, state_dict[key].clone().to(getattr(self, name).device))
         self._host_tables = None
+        self.__dict__["_lane_tables"] = {}
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
 
@@ -501,7 +604,44 @@ class GaussianConditional(_EntropyModelBase):
         if perm is not None:
             p = perm.long()
             sym, idx = sym.index_select(1, p), idx.index_select(1, p)
+        if STREAM_LANES:
+            return self._lanes_encode_begin(sym, idx, STREAM_LANES)()
         return self._encode_begin(sym, idx)()
+
+    def _lanes_encode_begin(self, sym, idx, lanes):
+        """The lane-parallel form of _encode_begin: prep -> encode -> pack on the GPU (pcc_rans_lanes_encode); only the two result
+        words and then the stream itself come to the host.  The first launch gives each lane scratch for 2 bytes per symbol;
+        a lane that outgrows it raises a flag and the call is repeated with the format's worst case."""
+        L = _lib.lib()
+        sym, idx = sym.contiguous(), idx.contiguous()
+        dev, n = sym.device, sym.numel()
+        tables = self.lane_tables(dev)
+
+        def launch(worst):
+            sb = check(L.pcc_rans_lanes_encode_scratch_bytes(n, lanes, worst))
+            ob = check(L.pcc_rans_lanes_encode_out_bytes(n, lanes, worst))
+            scratch, out, result = _lane_buffer("enc_scratch", sb, dev), _lane_buffer("enc_out", ob, dev), _lane_buffer("enc_result", 8, dev)
+            check(L.pcc_rans_lanes_encode(ptr(sym), ptr(idx), n, lanes, ptr(tables), worst, ptr(scratch), sb, ptr(out), ob, ptr(result),
+                                          _lib.stream()))
+            host, ev = _to_host_async(result[:8].view(torch.int32), "lanes_result")
+            return out, host, ev
+
+        first = launch(0)
+
+        def finish():
+            out, host, ev = first
+            ev.synchronize()
+            if int(host[1]) & 1:
+                global LANES_RETRIES
+                LANES_RETRIES += 1
+                out, host, ev = launch(1)
+                ev.synchronize()
+            nbytes, flags = int(host[0]), int(host[1])
+            if flags:
+                raise ValueError(f"lane-parallel y stream: the encoder reports {flags:#x} ({_lane_flag_text(flags)})")
+            return [_to_host(out[:nbytes], "lanes_stream").tobytes()]
+
+        return finish
 
     def _encode_begin(self, sym, idx):
         cdf, cdf_len, off = self.tables()
@@ -518,6 +658,13 @@ class GaussianConditional(_EntropyModelBase):
         One kernel writes the int16 symbol plane and the uint8 index plane in stream order (rows permuted on the way)
         into one buffer, one copy takes it to the host: 3 bytes per symbol instead of 8.  Symbols beyond int16 (legal,
         escape-coded, not seen with sane scales) fall back to the int32 planes."""
+        if STREAM_LANES:
+            # the lane-parallel stream: int32 planes in stream order stay on the device, the coder runs right behind them
+            sym, idx = self.encode_prep(y_feats, params)
+            if perm is not None:
+                p = perm.long()
+                sym, idx = sym.index_select(1, p), idx.index_select(1, p)
+            return self._lanes_encode_begin(sym, idx, STREAM_LANES)
         n, c = y_feats.shape
         dev = y_feats.device
         cn = c * n
@@ -548,6 +695,8 @@ class GaussianConditional(_EntropyModelBase):
         decode runs on a worker thread (the C call releases the GIL).  Returns a function that joins the
         thread, uploads the symbols and returns y_hat [N, C]; in between the caller can enqueue GPU
         work that does not depend on y (h_q, kernel maps of the first synthesis stage)."""
+        if STREAM_LANES:
+            return self._lanes_decode_begin(strings, params, c)
         n = params.shape[0]
         dev = params.device
         cn = c * n
@@ -585,6 +734,44 @@ class GaussianConditional(_EntropyModelBase):
             else:
                 sym = _to_device(wide.reshape(c, n), dev, "gc_sym_up")
                 check(_lib.lib().pcc_gc_dequantize(ptr(sym), ptr(params.contiguous()), n, c, ptr(yhat), _lib.stream()))
+            return yhat
+
+        return finish
+
+    def _lanes_decode(self, data, idx):
+        """PCL1 bytes + the device int32 index sequence -> (device int32 symbols like ``idx``, device status word); the header is
+        checked on the host before anything is enqueued, nothing waits for the GPU"""
+        if bytes(data[:4]) != LANES_MAGIC:
+            raise ValueError("PCC_STREAM_LANES / set_stream_lanes is set, so the y string must be a lane-parallel (PCL1) stream, and "
+                             "this one does not begin with its magic: it was coded in the reference's format (or is not a y "
+                             "string).  Encoder and decoder must agree: decode with set_stream_lanes(0)")
+        L = _lib.lib()
+        dev = idx.device
+        buf = np.frombuffer(data, dtype=np.uint8)
+        check(L.pcc_rans_lanes_header(ptr(buf), len(data)))
+        tables = self.lane_tables(dev)
+        stage = _pinned("lanes_up", len(data), torch.uint8)
+        stage.numpy()[:] = buf
+        up = stage.to(dev, non_blocking=True)
+        _upload_guard("lanes_up", dev)
+        sym = torch.empty_like(idx)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        check(L.pcc_rans_lanes_decode(ptr(buf), ptr(up), len(data), ptr(idx), idx.numel(), ptr(tables), ptr(sym), ptr(status),
+                                      _lib.stream()))
+        return sym, status
+
+    def _lanes_decode_begin(self, strings, params, c):
+        """The lane-parallel form of decompress_features_async: the stream's bytes go up, the index plane is built and the decode
+        (pcc_rans_lanes_decode) launched right behind what produced ``params``; nothing waits for the host and no job thread
+        runs.  The returned function only dequantises.  The decoder's status word is left for check_stream_status()."""
+        n = params.shape[0]
+        params = params.contiguous()
+        sym, status = self._lanes_decode(strings[0], self.indexes_for(params, c))
+        _threads.current().lane_status.append(status)
+
+        def finish():
+            yhat = torch.empty((n, c), dtype=torch.float32, device=params.device)
+            check(_lib.lib().pcc_gc_dequantize(ptr(sym), ptr(params), n, c, ptr(yhat), _lib.stream()))
             return yhat
 
         return finish

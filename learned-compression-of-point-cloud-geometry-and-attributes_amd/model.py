@@ -14,6 +14,7 @@ import struct
 import torch
 import torch.nn as nn
 
+from . import entropy as _entropy
 from . import octree
 from . import sparse as sp
 from .entropy_models import MeanScaleHyperprior, MeanScaleHyperprior_Map, _canonical_map
@@ -141,7 +142,9 @@ class ColorModel(nn.Module):
             points = [_canonical_map(c8, 8), _canonical_map(c32, 32)]          # model/model.py:197-201: both models decode on the same lists
             y_hat = self.entropy_model.decompress(points, strings[0], shape[0])
             Q_hat = self.entropy_model_map.decompress(points, strings[1], shape[1])
-        return self.reconstruct(y_hat, Q_hat, k, return_batch)
+        out = self.reconstruct(y_hat, Q_hat, k, return_batch)
+        _entropy.check_stream_status()          # (lane-parallel y streams: the decoder's status word, read once, behind g_s; else nothing)
+        return out
 
     @torch.no_grad()
     def reconstruct(self, y_hat, Q_hat, k, return_batch=False):
