@@ -313,6 +313,13 @@ int64_t pcc_conv_wgrad_scratch_elems(int32_t K, int32_t cin, int32_t cout);
 int pcc_conv_wgrad(const float* fin, int64_t n_in, int32_t cin, const float* dy, int64_t n_out, int32_t cout,
                    const int32_t* nbr, const int32_t* order, const uint32_t* group_mask32, int32_t K, float* dw,
                    float* scratch, int64_t scratch_elems, void* stream);
+/* The kernel a weight-gradient launch runs on this shape (bf16 = 0: pcc_conv_wgrad, 1: pcc_conv_wgrad_bf16), spelled as the
+ * profiler prints it, e.g. "conv_wgrad_slice_kernel<5, 2>", written to `buf` (`len` bytes; buf == NULL leaves it out);
+ * *split = row-group splits of the launch, *partials = images [K][cin][cout] its second stage adds (either may be NULL).
+ * n_out <= 0 gives an empty name and zeros: the launch only zero-fills dw.  Host only, launches nothing.  A shape the launch
+ * refuses gives the launch's error code. */
+int pcc_conv_wgrad_kernel_name(int32_t bf16, int32_t K, int32_t cin, int32_t cout, int64_t n_out, char* buf, int32_t len,
+                               int32_t* split, int32_t* partials);
 /* bf16 operands (fin, dy bf16; cin, cout multiples of 64), fp32 accumulation and result; same scratch size. */
 int pcc_conv_wgrad_bf16(const uint16_t* fin, int64_t n_in, int32_t cin, const uint16_t* dy, int64_t n_out, int32_t cout,
                         const int32_t* nbr, const int32_t* order, const uint32_t* group_mask32, int32_t K, float* dw,

@@ -67,6 +67,7 @@ SIGNATURES = {
     "pcc_sort_coords": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),
     "pcc_kernel_map_transpose": (c_int, [c_void_p, c_i64, c_i32, c_i64, c_void_p, c_void_p, c_void_p]),
     "pcc_conv_wgrad_scratch_elems": (c_i64, [c_i32, c_i32, c_i32]),
+    "pcc_conv_wgrad_kernel_name": (c_int, [c_i32, c_i32, c_i32, c_i32, c_i64, ctypes.c_char_p, c_i32, c_void_p, c_void_p]),
     "pcc_conv_wgrad": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
                                c_i64, c_void_p]),
     "pcc_conv_wgrad_bf16": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,

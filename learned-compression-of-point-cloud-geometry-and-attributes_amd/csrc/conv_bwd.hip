@@ -738,26 +738,122 @@ static inline int wgrad_splits(int64_t n_out) {            // at least ~48 row g
     const int64_t want = ((n_out + 31) / 32) / 48;
     return (int)(want < 8 ? 8 : (want > WG_SPLIT_MAX ? WG_SPLIT_MAX : want));
 }
-// slice kernel (nine offsets = one dz plane per workgroup, dY rows staged once per group): the default for 64-channel-class
-// blocks of a 27-offset kernel; PCC_WGRAD_SLICE=0 keeps the one-offset kernel for A/B runs
-static inline bool wgrad_slice(int cin, int cout, int K) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("PCC_WGRAD_SLICE"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on && wgrad_rowsplit(cin, cout) && K == 27;
-}
 constexpr int WG_SPLIT_SLICE_MAX = 256;
 static inline int wgrad_slice_splits(int64_t n_out) {      // three workgroup sets only: more splits to fill 256 CUs x 4
     const int64_t want = ((n_out + 31) / 32) / 24;
     return (int)(want < 8 ? 8 : (want > WG_SPLIT_SLICE_MAX ? WG_SPLIT_SLICE_MAX : want));
 }
-static inline int wgrad_partials(int cin, int cout, int split, int K) {
-    if (!wgrad_mfma(cin, cout)) return WG_SPLIT_THIN;
-    if (wgrad_slice(cin, cout, K)) return split;
-    return split * (wgrad_rowsplit(cin, cout) ? 4 : 1);
+
+// ---------------------------------------------------------------------------------------------
+// The plan of a weight-gradient launch: which kernel, how many row-group splits, how many partial images the second stage
+// adds.  One place: the launches (pcc_conv_wgrad, pcc_conv_wgrad_bf16) and their names (pcc_conv_wgrad_kernel_name) follow it.
+// The A/B switches are read once per process:
+//   PCC_WGRAD_SLICE=0             keeps the one-offset kernel for 64-channel-class blocks of a 27-offset kernel (fp32)
+//   PCC_WGRAD_SLICE_O=3|4|5|6|9   offsets per workgroup of the fp32 slice kernel (accumulators = 16 O registers per lane); 5
+//   PCC_WGRAD_AHEAD=1|2           prefetch distance of its gathers; 2
+//   PCC_WGRAD_BF16_SLICE_O=0|3|5|9  bf16 64 -> 64, 27 offsets: 0 keeps the one-offset kernel; 3.  850 k-row / 265 k-row shells,
+//       same box: one-offset 122-124 / 129 TFLOP/s, O = 3 137 / 135 (71 registers, 7 waves per SIMD), O = 5 121 / 119 (103
+//       registers), O = 9 140 / 125 (167 registers): fewer bytes and fewer waves trade evenly
+// ---------------------------------------------------------------------------------------------
+enum WgradFamily { WGF_THIN, WGF_ONE, WGF_SLICE, WGF_BF16_ONE, WGF_BF16_SLICE };
+
+struct WgradPlan {
+    WgradFamily family;
+    int O, ahead;         // slice kernels: offsets per workgroup; fp32 slice: steps the gathers run ahead
+    int split;            // row-group splits (the thin kernel: WG_SPLIT_THIN row ranges)
+    int partials;         // images [K][cin][cout] in the scratch
+};
+
+static inline bool wgrad_slice_on() {
+    static int on = -1;
+    if (on < 0) { const char* e = getenv("PCC_WGRAD_SLICE"); on = (e && e[0] == '0') ? 0 : 1; }
+    return on != 0;
+}
+static inline int wgrad_slice_o() {
+    static int O = -1;
+    if (O < 0) {
+        const char* e = getenv("PCC_WGRAD_SLICE_O");
+        O = e ? atoi(e) : 5;
+        if (O != 3 && O != 4 && O != 6 && O != 9) O = 5;
+    }
+    return O;
+}
+static inline int wgrad_ahead() {
+    static int ahead = -1;
+    if (ahead < 0) { const char* e = getenv("PCC_WGRAD_AHEAD"); ahead = (e && e[0] == '1') ? 1 : 2; }
+    return ahead;
+}
+static inline int wgrad_bf16_slice_o() {
+    static int slice_o = -1;
+    if (slice_o < 0) {
+        const char* e = getenv("PCC_WGRAD_BF16_SLICE_O");
+        slice_o = e ? atoi(e) : 3;
+        if (slice_o != 0 && slice_o != 3 && slice_o != 5 && slice_o != 9) slice_o = 3;
+    }
+    return slice_o;
+}
+// slice kernel (O offsets per workgroup, dY rows staged once per group): the default for 64-channel-class blocks of a
+// 27-offset kernel
+static inline bool wgrad_slice(int cin, int cout, int K) { return wgrad_slice_on() && wgrad_rowsplit(cin, cout) && K == 27; }
+
+// shape checks of a launch and its plan (n_out >= 1)
+static int plan_wgrad(bool bf16, int K, int cin, int cout, int64_t n_out, WgradPlan& p) {
+    p.O = 0; p.ahead = 0;
+    if (bf16) {
+        PCC_REQUIRE(K >= 1 && K <= 27, "pcc_conv_wgrad_bf16: bad K");
+        PCC_REQUIRE(cin % 64 == 0 && cout % 64 == 0 && cin >= 64 && cout >= 64, "pcc_conv_wgrad_bf16: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
+        if (wgrad_bf16_slice_o() && cin == 64 && cout == 64 && K == 27) {
+            p.family = WGF_BF16_SLICE;
+            p.O = wgrad_bf16_slice_o();
+            p.split = wgrad_slice_splits(n_out);
+        } else {
+            p.family = WGF_BF16_ONE;
+            p.split = wgrad_splits(n_out);
+        }
+        p.partials = p.split;
+        return PCC_OK;
+    }
+    PCC_REQUIRE(K >= 1 && K <= 27 && cin >= 1 && cout >= 1, "pcc_conv_wgrad: bad shape");
+    if (!wgrad_mfma(cin, cout)) {
+        PCC_REQUIRE((int64_t)cin * cout <= 4096, "pcc_conv_wgrad: thin path handles cin * cout <= 4096 (got %d x %d)", cin, cout);
+        p.family = WGF_THIN;
+        p.split = p.partials = WG_SPLIT_THIN;
+    } else if (wgrad_slice(cin, cout, K)) {
+        p.family = WGF_SLICE;
+        p.O = wgrad_slice_o();
+        p.ahead = wgrad_ahead();
+        p.split = p.partials = wgrad_slice_splits(n_out);
+    } else {
+        p.family = WGF_ONE;
+        p.split = wgrad_splits(n_out);
+        p.partials = p.split * (wgrad_rowsplit(cin, cout) ? 4 : 1);     // two row groups per iteration, one partial per wave
+    }
+    return PCC_OK;
 }
 
 int64_t pcc_conv_wgrad_scratch_elems(int32_t K, int32_t cin, int32_t cout) {
-    return (int64_t)wgrad_partials(cin, cout, WG_SPLIT_MAX, 0) * K * cin * cout;      // the larger of the two layouts
+    // the largest layout any plan of the shape uses: WG_SPLIT_MAX x 4 rowsplit partials >= WG_SPLIT_SLICE_MAX slice partials
+    const int partials = !wgrad_mfma(cin, cout) ? WG_SPLIT_THIN : WG_SPLIT_MAX * (wgrad_rowsplit(cin, cout) ? 4 : 1);
+    return (int64_t)partials * K * cin * cout;
+}
+
+int pcc_conv_wgrad_kernel_name(int32_t bf16, int32_t K, int32_t cin, int32_t cout, int64_t n_out, char* buf, int32_t len,
+                               int32_t* split, int32_t* partials) {
+    WgradPlan p;
+    if (int rc = plan_wgrad(bf16 != 0, K, cin, cout, n_out, p)) return rc;
+    if (n_out <= 0) { p.split = p.partials = 0; }             // no kernel: the launch zero-fills dw
+    if (split) *split = p.split;
+    if (partials) *partials = p.partials;
+    if (buf == nullptr) return PCC_OK;
+    int n;
+    if (n_out <= 0) n = snprintf(buf, len, "%s", "");
+    else if (p.family == WGF_THIN) n = snprintf(buf, len, "conv_wgrad_thin_kernel");
+    else if (p.family == WGF_ONE) n = snprintf(buf, len, "conv_wgrad_kernel");
+    else if (p.family == WGF_SLICE) n = snprintf(buf, len, "conv_wgrad_slice_kernel<%d, %d>", p.O, p.ahead);
+    else if (p.family == WGF_BF16_ONE) n = snprintf(buf, len, "conv_wgrad_bf16_kernel");
+    else n = snprintf(buf, len, "conv_wgrad_bf16_slice_kernel<%d>", p.O);
+    PCC_REQUIRE(n < len, "pcc_conv_wgrad_kernel_name: %d bytes do not hold the name", len);
+    return PCC_OK;
 }
 
 int pcc_conv_wgrad(const float* fin, int64_t n_in, int32_t cin, const float* dy, int64_t n_out, int32_t cout, const int32_t* nbr,
@@ -772,41 +868,37 @@ int pcc_conv_wgrad(const float* fin, int64_t n_in, int32_t cin, const float* dy,
         PCC_CHECK_HIP(hipMemsetAsync(dw, 0, (size_t)elems * sizeof(float), st));
         return PCC_OK;
     }
+    WgradPlan p;
+    if (int rc = plan_wgrad(false, K, cin, cout, n_out, p)) return rc;
     WgradArgs a;
     a.fin = fin; a.dy = dy; a.nbr = nbr; a.order = order; a.gmask = group_mask32; a.partial = scratch;
-    a.n_in = n_in; a.n_out = n_out; a.cin = cin; a.cout = cout; a.K = K; a.split = wgrad_splits(n_out);
-    if (cin % 32 == 0 && cout % 32 == 0) {
+    a.n_in = n_in; a.n_out = n_out; a.cin = cin; a.cout = cout; a.K = K; a.split = p.split;
+    if (p.family != WGF_THIN) {
         PCC_REQUIRE((uint64_t)n_in * cin * 4 <= WG_OOB && (uint64_t)n_out * cout * 4 <= WG_OOB,
                     "pcc_conv_wgrad: operands of 4 GiB and more are not supported yet");
         PCC_REQUIRE(((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0,
                     "pcc_conv_wgrad: fin and dy must be 16-byte aligned (16-byte LDS-DMA loads)");
-        if (wgrad_slice(cin, cout, K)) {
-            static int O = -1;       // PCC_WGRAD_SLICE_O=3|5|9: offsets per workgroup (A/B; accumulators = 16 O registers per lane)
-            if (O < 0) { const char* e = getenv("PCC_WGRAD_SLICE_O"); O = e ? atoi(e) : 5; }
-            a.split = wgrad_slice_splits(n_out);
-            static int ahead = -1;   // PCC_WGRAD_AHEAD=1|2: prefetch distance of the gathers (A/B)
-            if (ahead < 0) { const char* e = getenv("PCC_WGRAD_AHEAD"); ahead = (e && e[0] == '1') ? 1 : 2; }
+    }
+    if (p.family == WGF_SLICE) {
 #define PCC_SLICE(OO)                                                                                                              \
     do {                                                                                                                           \
         const dim3 grid((unsigned)(((27 + OO - 1) / OO) * a.split));                                                               \
-        if (ahead == 1) hipLaunchKernelGGL((conv_wgrad_slice_kernel<OO, 1>), grid, dim3(256), 2 * 2 * 2048 * sizeof(float), st, a); \
+        if (p.ahead == 1) hipLaunchKernelGGL((conv_wgrad_slice_kernel<OO, 1>), grid, dim3(256), 2 * 2 * 2048 * sizeof(float), st, a); \
         else hipLaunchKernelGGL((conv_wgrad_slice_kernel<OO, 2>), grid, dim3(256), 2 * 3 * 2048 * sizeof(float), st, a);            \
     } while (0)
-            if (O == 3) PCC_SLICE(3);
-            else if (O == 4) PCC_SLICE(4);
-            else if (O == 6) PCC_SLICE(6);
-            else if (O == 9) PCC_SLICE(9);
-            else PCC_SLICE(5);
+        if (p.O == 3) PCC_SLICE(3);
+        else if (p.O == 4) PCC_SLICE(4);
+        else if (p.O == 6) PCC_SLICE(6);
+        else if (p.O == 9) PCC_SLICE(9);
+        else PCC_SLICE(5);
 #undef PCC_SLICE
-        } else {
-            const dim3 grid((unsigned)(K * a.split), (unsigned)((cin + 127) / 128), (unsigned)((cout + 127) / 128));
-            hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 8 * 1024 * sizeof(float), st, a);
-        }
+    } else if (p.family == WGF_ONE) {
+        const dim3 grid((unsigned)(K * a.split), (unsigned)((cin + 127) / 128), (unsigned)((cout + 127) / 128));
+        hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 8 * 1024 * sizeof(float), st, a);
     } else {
-        PCC_REQUIRE((int64_t)cin * cout <= 4096, "pcc_conv_wgrad: thin path handles cin * cout <= 4096 (got %d x %d)", cin, cout);
         hipLaunchKernelGGL(conv_wgrad_thin_kernel, dim3((unsigned)(K * WG_SPLIT_THIN)), dim3(256), 0, st, a);
     }
-    launch_wgrad_reduce(scratch, elems, wgrad_partials(cin, cout, a.split, K), dw, st);
+    launch_wgrad_reduce(scratch, elems, p.partials, dw, st);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
 }
@@ -814,8 +906,8 @@ int pcc_conv_wgrad(const float* fin, int64_t n_in, int32_t cin, const float* dy,
 int pcc_conv_wgrad_bf16(const uint16_t* fin, int64_t n_in, int32_t cin, const uint16_t* dy, int64_t n_out, int32_t cout,
                         const int32_t* nbr, const int32_t* order, const uint32_t* group_mask32, int32_t K, float* dw, float* scratch,
                         int64_t scratch_elems, void* stream) {
-    PCC_REQUIRE(K >= 1 && K <= 27, "pcc_conv_wgrad_bf16: bad K");
-    PCC_REQUIRE(cin % 64 == 0 && cout % 64 == 0 && cin >= 64 && cout >= 64, "pcc_conv_wgrad_bf16: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
+    WgradPlan p;
+    if (int rc = plan_wgrad(true, K, cin, cout, n_out, p)) return rc;
     PCC_REQUIRE(nbr != nullptr, "pcc_conv_wgrad_bf16: neighbour table required");
     PCC_REQUIRE((uint64_t)n_in * cin * 2 <= WG_OOB && (uint64_t)n_out * cout * 2 <= WG_OOB, "pcc_conv_wgrad_bf16: operands of 4 GiB and more are not supported");
     PCC_REQUIRE(((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0,
@@ -829,32 +921,19 @@ int pcc_conv_wgrad_bf16(const uint16_t* fin, int64_t n_in, int32_t cin, const ui
     WgradArgs a;
     a.fin = reinterpret_cast<const float*>(fin); a.dy = reinterpret_cast<const float*>(dy); a.nbr = nbr; a.order = order;
     a.gmask = group_mask32; a.partial = scratch; a.n_in = n_in; a.n_out = n_out; a.cin = cin; a.cout = cout; a.K = K;
-    a.split = wgrad_splits(n_out);
-    PCC_REQUIRE(scratch_elems >= (int64_t)a.split * elems, "pcc_conv_wgrad_bf16: scratch too small");
-    // 64 -> 64, 27 offsets: the slice kernel (PCC_WGRAD_BF16_SLICE_O=0 keeps the one-offset kernel; 3 | 5 | 9 offsets per
-    // workgroup).  850 k-row / 265 k-row shells, same box: one-offset 122-124 / 129 TFLOP/s, O = 3 137 / 135 (71 registers, 7 waves
-    // per SIMD), O = 5 121 / 119 (103 registers), O = 9 140 / 125 (167 registers): fewer bytes and fewer waves trade evenly
-    static int slice_o = -1;
-    if (slice_o < 0) {
-        const char* e = getenv("PCC_WGRAD_BF16_SLICE_O");
-        slice_o = e ? atoi(e) : 3;
-        if (slice_o != 0 && slice_o != 3 && slice_o != 5 && slice_o != 9) slice_o = 3;
-    }
-    if (slice_o && cin == 64 && cout == 64 && K == 27) {
-        a.split = wgrad_slice_splits(n_out);
-        PCC_REQUIRE(scratch_elems >= (int64_t)a.split * elems, "pcc_conv_wgrad_bf16: scratch too small");
-        const unsigned sets = (unsigned)((K + slice_o - 1) / slice_o);
-        const size_t lds = (size_t)(slice_o + 1) * 2048 * sizeof(unsigned short);
-        if (slice_o == 3) hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<3>, dim3(sets * a.split), dim3(256), lds, st, a);
-        else if (slice_o == 5) hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<5>, dim3(sets * a.split), dim3(256), lds, st, a);
+    a.split = p.split;
+    PCC_REQUIRE(scratch_elems >= (int64_t)p.partials * elems, "pcc_conv_wgrad_bf16: scratch too small");
+    if (p.family == WGF_BF16_SLICE) {
+        const unsigned sets = (unsigned)((K + p.O - 1) / p.O);
+        const size_t lds = (size_t)(p.O + 1) * 2048 * sizeof(unsigned short);
+        if (p.O == 3) hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<3>, dim3(sets * a.split), dim3(256), lds, st, a);
+        else if (p.O == 5) hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<5>, dim3(sets * a.split), dim3(256), lds, st, a);
         else hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<9>, dim3(sets * a.split), dim3(256), lds, st, a);
-        launch_wgrad_reduce(scratch, elems, a.split, dw, st);
-        PCC_LAUNCH_CHECK();
-        return PCC_OK;
+    } else {
+        const dim3 grid((unsigned)(K * a.split), (unsigned)((cin + 127) / 128), (unsigned)((cout + 127) / 128));
+        hipLaunchKernelGGL(conv_wgrad_bf16_kernel, grid, dim3(256), 4 * 2048 * sizeof(unsigned short), st, a);
     }
-    const dim3 grid((unsigned)(K * a.split), (unsigned)((cin + 127) / 128), (unsigned)((cout + 127) / 128));
-    hipLaunchKernelGGL(conv_wgrad_bf16_kernel, grid, dim3(256), 4 * 2048 * sizeof(unsigned short), st, a);
-    launch_wgrad_reduce(scratch, elems, a.split, dw, st);
+    launch_wgrad_reduce(scratch, elems, p.partials, dw, st);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
 }
