@@ -326,6 +326,28 @@ int pcc_conv_wgrad_bf16(const uint16_t* fin, int64_t n_in, int32_t cin, const ui
                         float* scratch, int64_t scratch_elems, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Channelwise (depthwise) window convolution on ONE coordinate set, stride 1, and its adjoint
+ * (ME.MinkowskiChannelwiseConvolution: the window sums of ColorSSIM, loss.py:204-206, 391-453).
+ *   y[i, ch] = sum_k w[k', ch] * x[row(coords[i] + offset(k) * tensor_stride), ch]
+ * over the offsets whose voxel exists in the set (absent neighbours, and neighbours whose coordinate
+ * leaves the key range, contribute nothing; the batch index is part of the key, so a window never
+ * crosses batch items).  k = (dx+h) + ksize (dy+h) + ksize^2 (dz+h), h = ksize / 2 (x fastest);
+ * k' = k for flip = 0 and ksize^3 - 1 - k for flip = 1.  Input and output set are the same, so
+ * flip = 1 with the same window is exactly the adjoint: backward-data is this call on dY.
+ * x, y [n, c] fp32 (c = 1 .. 32); coords [n, 4] and (keys, vals, cap, tensor_stride) the set and its
+ * table (vals = row of x); w [ksize^3, w_channels] with w_channels = 1 (one window for every channel)
+ * or c; ksize odd, 1 .. 11.  Anything else is refused before any launch (PCC_ERR_UNSUPPORTED for a
+ * kernel size or channel count outside the range, else PCC_ERR_ARG); n == 0 launches nothing.
+ * The neighbour table is never stored: one kernel probes and accumulates.  Deterministic, no atomics:
+ * an element starts at +0 and adds its present neighbours' products one by one in ascending
+ * (dz+h) + ksize (dy+h) + ksize^2 (dx+h) — z fastest, for either flip — each product rounded to fp32
+ * before the add (separate multiply and add, no fused multiply-add).
+ * ------------------------------------------------------------------------------------- */
+int pcc_chconv(const float* x, int64_t n, int32_t c, const int32_t* coords, const uint64_t* keys, const int32_t* vals,
+               int64_t cap, int32_t tensor_stride, int32_t ksize, const float* w, int32_t w_channels, int32_t flip,
+               float* y, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Latent-coordinate side channel of file mode.  Replaces ColorModel.gpcc_encode / gpcc_decode
  * (model/model.py:318-395), which shell out to the external MPEG G-PCC binary `tmc3`; this is the
  * build's own lossless octree ("PCO1", NOT G-PCC compatible; container in octree.py).

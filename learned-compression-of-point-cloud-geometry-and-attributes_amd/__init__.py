@@ -13,7 +13,8 @@ Public surface (mirrors /root/reference/model/): ``ColorModel``, ``SparseTensor`
 from . import _lib
 from ._lib import build, lib  # noqa: F401
 from .sparse import (CoordMap, SparseTensor, MinkowskiConvolution, MinkowskiConvolutionTranspose,  # noqa: F401
-                     MinkowskiGenerativeConvolutionTranspose, MinkowskiPruning, MinkowskiReLU, MinkowskiLeakyReLU)
+                     MinkowskiGenerativeConvolutionTranspose, MinkowskiChannelwiseConvolution, MinkowskiPruning, MinkowskiReLU,
+                     MinkowskiLeakyReLU)
 from .entropy import EntropyBottleneck, GaussianConditional  # noqa: F401
 from .blocks import ScaledBlock, GenerativeUpBlock, ConditionEncoder  # noqa: F401
 from .transforms import AnalysisTransform, SparseSynthesisTransform  # noqa: F401

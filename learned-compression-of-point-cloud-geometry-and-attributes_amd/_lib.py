@@ -72,6 +72,7 @@ SIGNATURES = {
                                c_i64, c_void_p]),
     "pcc_conv_wgrad_bf16": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
                                     c_i64, c_void_p]),
+    "pcc_chconv": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p]),
     "pcc_octree_scratch_bytes": (c_i64, [c_i64]),
     "pcc_octree_occupancy": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "pcc_octree_expand": (c_int, [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),
@@ -110,6 +111,7 @@ def build(force=False):
     subprocess.check_call(args)
     check_kernel_resources()
     check_kernel_resources(os.path.join(_HERE, "build", "rans_lanes.resources.txt"), LANE_KERNELS)
+    check_kernel_resources(os.path.join(_HERE, "build", "chconv.resources.txt"), CHCONV_KERNELS)
     check_small_kernel_lds_reads()
     return SO_PATH
 
@@ -121,6 +123,9 @@ NO_SCRATCH_KERNELS = ("conv_small_kernel", "conv_mfma_buf_kernel", "conv_mfma_ke
 # the lane-parallel range coder (csrc/rans_lanes.hip): one thread carries one serial state chain, and a spilled state or
 # batch register would put a scratch round trip into every link of it
 LANE_KERNELS = ("rans_lanes_encode_kernel", "rans_lanes_pack_kernel", "rans_lanes_decode_kernel")
+# the channelwise window convolution (csrc/chconv.hip): up to 1,331 probes and adds per output element run out of one
+# accumulator and a handful of probe registers, and a spill would sit inside that loop
+CHCONV_KERNELS = ("chconv_kernel",)
 
 
 def check_small_kernel_lds_reads(obj=None):

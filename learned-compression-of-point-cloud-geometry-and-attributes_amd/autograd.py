@@ -8,6 +8,9 @@ in model/, driven by train.py:194-206).  Here one ``torch.autograd.Function`` wr
               dW[k] = sum over pairs of X[i]^T dY[j]                      pcc_conv_wgrad
               db  = column sums of dY
 
+The channelwise window convolution of the ColorSSIM loss (``ChannelwiseConvFn``) is its own node on pcc_chconv: forward
+with the window as given, backward-data the same kernel on dY with the window flipped.
+
 Activations, FiLM and residuals — fused into the convolution's epilogue on the inference path — are
 ordinary torch ops here so that autograd differentiates them.
 """
@@ -261,3 +264,30 @@ def epilogue_train(c, film, residual, act):
 def conv_train(x_feats, in_map, out_map, layer, ksize, transposed, out_channels=None):
     """differentiable out = bias + conv(x) on the HIP kernels"""
     return SparseConvFn.apply(x_feats, layer.kernel, layer.bias, in_map, out_map, ksize, transposed, out_channels)
+
+
+def chconv_launch(feats, cmap, window, ksize, flip):
+    """y = pcc_chconv(feats) on the set ``cmap`` with ``window`` [ksize^3, 1 or C]; flip = 1 is the adjoint"""
+    n, c = feats.shape
+    keys, vals, cap = cmap.table()
+    out = torch.empty((n, c), dtype=torch.float32, device=feats.device)
+    check(_lib.lib().pcc_chconv(ptr(feats), n, c, ptr(cmap.coords), ptr(keys), ptr(vals), cap, cmap.stride, ksize, ptr(window),
+                                window.shape[1], flip, ptr(out), _lib.stream()))
+    return out
+
+
+class ChannelwiseConvFn(torch.autograd.Function):
+    """y[i, ch] = sum_k window[k, ch] * x[nbr(i, k), ch] on one coordinate set (csrc/chconv.hip).  Input and output set are
+    the same, so the backward with respect to x is the same kernel on dY with the window index reversed (flip = 1).  The
+    window gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, feats, window, cmap, ksize):
+        ctx.save_for_backward(window)
+        ctx.cmap, ctx.ksize = cmap, ksize
+        return chconv_launch(feats.contiguous(), cmap, window, ksize, 0)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (window,) = ctx.saved_tensors
+        return chconv_launch(dy.contiguous(), ctx.cmap, window, ctx.ksize, 1), None, None, None

@@ -3,7 +3,7 @@
 Host-side mirror of the MinkowskiEngine surface the reference uses:
 ``SparseTensor`` (``.C``, ``.F``, ``.tensor_stride``, ``.device``, ``.coordinate_manager``,
 ``.features_at_coordinates``), ``MinkowskiConvolution``, ``MinkowskiGenerativeConvolutionTranspose``,
-``MinkowskiConvolutionTranspose``, ``MinkowskiPruning``, ``MinkowskiReLU`` / ``MinkowskiLeakyReLU``.
+``MinkowskiConvolutionTranspose``, ``MinkowskiChannelwiseConvolution``, ``MinkowskiPruning``, ``MinkowskiReLU`` / ``MinkowskiLeakyReLU``.
 Layer parameters keep ME's names and shapes (``kernel`` [K, C_in, C_out] or [C_in, C_out] for
 kernel_size 1, ``bias`` [1, C_out]) so reference state_dicts load unchanged.
 
@@ -941,6 +941,46 @@ class MinkowskiConvolutionTranspose(_ConvBase):
     """ME.MinkowskiConvolutionTranspose (model/entropy_models.py:298,302).  Output coordinates are
     generated like the generative variant (decode semantics)."""
     transposed = True
+
+
+class MinkowskiChannelwiseConvolution(nn.Module):
+    """ME.MinkowskiChannelwiseConvolution (the window sums of ColorSSIM, loss.py:204-206): every channel is convolved with
+    its own column of ``kernel`` [kernel_size^3, in_channels] (ME's layout; offsets x fastest).  A kernel assigned with shape
+    [kernel_size^3, 1] is one window for every channel, which is how the reference's loss sets it.
+
+    One HIP kernel probes the set's table and accumulates (csrc/chconv.hip): no neighbour table is stored.  Only stride 1,
+    dilation 1 and no bias are built.  The input's gradient is the same kernel with the window flipped; the KERNEL's gradient
+    is not built: a kernel that requires grad raises NotImplementedError while autograd is tracking (freeze it, as the
+    loss does)."""
+
+    def __init__(self, in_channels, kernel_size=-1, stride=1, dilation=1, bias=False, dimension=3):
+        super().__init__()
+        if stride != 1 or dilation != 1 or bias or dimension != 3:
+            raise NotImplementedError("MinkowskiChannelwiseConvolution: only stride=1, dilation=1, bias=False, dimension=3")
+        self.in_channels, self.kernel_size = int(in_channels), int(kernel_size)
+        if self.kernel_size < 1 or self.kernel_size % 2 == 0 or self.kernel_size > 11:
+            raise NotImplementedError("MinkowskiChannelwiseConvolution: kernel_size must be odd, 1 .. 11")
+        self.kernel = nn.Parameter(torch.empty((self.kernel_size ** 3, self.in_channels), dtype=torch.float32))
+        bound = 1.0 / math.sqrt(self.kernel_size ** 3)          # ME default: U(-1/sqrt(n), 1/sqrt(n)), n = kernel volume
+        with torch.no_grad():
+            self.kernel.uniform_(-bound, bound)
+
+    def forward(self, x):
+        from .autograd import ChannelwiseConvFn, chconv_launch
+        kernel = self.kernel
+        c = x.F.shape[1]
+        if kernel.dim() != 2 or kernel.shape[0] != self.kernel_size ** 3 or kernel.shape[1] not in (1, c):
+            raise ValueError(f"kernel of shape {tuple(kernel.shape)} on {c} channels: need [{self.kernel_size ** 3}, 1 or {c}]")
+        _require_cuda(kernel)
+        if torch.is_grad_enabled() and kernel.requires_grad:
+            raise NotImplementedError("MinkowskiChannelwiseConvolution: the kernel's gradient is not built; "
+                                      "set kernel.requires_grad = False")
+        window = kernel.detach().to(torch.float32).contiguous()
+        if _tracked(x.F):
+            feats = ChannelwiseConvFn.apply(x.F, window, x.map, self.kernel_size)
+        else:
+            feats = chconv_launch(x.F.contiguous(), x.map, window, self.kernel_size, 0)
+        return SparseTensor._wrap(feats, x.map)
 
 
 class MinkowskiReLU(nn.Module):
