@@ -387,6 +387,50 @@ int pcc_nn_search(const int32_t* query, int64_t nq, const uint64_t* keys, const 
                   int32_t* tie_count, double* tie_rgb, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * View rendering and view metrics of the view-dependent / region-of-interest evaluation
+ * (evaluate_view_dep.py:102-305).
+ *
+ * pcc_render_view replaces render_pointviews (evaluate_view_dep.py:308-348, an open3d OpenGL window) by an
+ * exact orthographic z-buffer splat of ONE voxelised cloud along a signed coordinate axis (every view of
+ * evaluate_view_dep.py:46-57 is one).  coords [n,4] (the batch column is ignored), rgb8 uint8 [n,3];
+ * right / up / front: HOST int32[3], signed unit axes, mutually orthogonal, right == up x front; front points
+ * from the object to the camera (open3d's set_front).  For a row p: u = right.p, v = up.p, d = front.p; the
+ * point covers columns (u - u_min) * scale + ox + i and rows (v_max - v) * scale + oy + j for i, j in
+ * [0, point_size); pixels outside the image are dropped one by one (no wrap, a partly visible point is not
+ * rejected whole).  A pixel shows the point with the largest d and, among equal d, the lowest row index;
+ * untouched pixels show `background` (HOST, 3 bytes).  scratch: the z-buffer, uint64 [H*W] =
+ * pcc_render_scratch_bytes(H, W) bytes (0 for a size the call refuses); image: uint8 [H,W,3].  All integer and
+ * bitwise reproducible: the splat is a 64-bit atomic maximum of ((d + 2^18) << 32) | (0xFFFFFFFF - row), which
+ * does not depend on arrival order.  A row with a coordinate beyond PCC_COORD_LIMIT draws nothing.
+ * Refused before any launch (PCC_ERR_ARG): vectors that are no signed unit axes or not orthogonal, right !=
+ * up x front, scale outside 1..64, point_size outside 1..16, H or W outside 1..8192, n above 2^32 - 2, a null
+ * cloud with n > 0, a null or short z-buffer, a null image.  n == 0 is valid: every pixel is background.
+ *
+ * pcc_image_compare replaces skimage's rgb2yuv, peak_signal_noise_ratio and structural_similarity
+ * (evaluate_view_dep.py:196-204, 243-249, 288-294) by their raw sums in float64 for two uint8 [H,W,3] images,
+ * the reference view and the test view.  Per pixel and channel f = byte / 255.0 and YUV = (f_r m0 + f_g m1) +
+ * f_b m2 with skimage's yuv_from_rgb rows, separate multiplies and adds.  out (device double[8]): [0..2] the
+ * per-channel sums of squared differences over all pixels, [3..5] the per-channel sums of the SSIM map of
+ * structural_similarity(win_size=7, data_range=1.0, gaussian_weights=False, use_sample_covariance=True) over
+ * its crop, the interior (H-6) x (W-6) (7 x 7 window means of X, Y, XX, YY, XY; variances and covariance
+ * 49/48 (mean of product - product of means); C1 = 1e-4, C2 = 9e-4; S = ((2 ux uy + C1)(2 vxy + C2)) /
+ * ((ux^2 + uy^2 + C1)(vx + vy + C2))), [6] and [7] the smallest and the largest YUV value of `ref`.
+ * Workgroups own pcc_image_compare_tile() x pcc_image_compare_tile() pixels and store their partial sums in
+ * workgroup order in scratch (pcc_image_compare_scratch_bytes(H, W) bytes; 0 for a size the call refuses); a
+ * final pass adds them in ascending order.  No float atomics: bitwise reproducible.  Refused before any
+ * launch: H or W below 7 or above 8192, null pointers, a short scratch.
+ * ------------------------------------------------------------------------------------- */
+int64_t pcc_render_scratch_bytes(int32_t H, int32_t W);
+int pcc_render_view(const int32_t* coords, const uint8_t* rgb8, int64_t n, const int32_t* right, const int32_t* up,
+                    const int32_t* front, int32_t u_min, int32_t v_max, int32_t ox, int32_t oy, int32_t scale,
+                    int32_t point_size, int32_t H, int32_t W, const uint8_t* background, void* scratch,
+                    int64_t scratch_bytes, uint8_t* image, void* stream);
+int32_t pcc_image_compare_tile(void);
+int64_t pcc_image_compare_scratch_bytes(int32_t H, int32_t W);
+int pcc_image_compare(const uint8_t* ref, const uint8_t* img, int32_t H, int32_t W, void* scratch,
+                      int64_t scratch_bytes, double* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Entropy model, device side (compressai EntropyBottleneck / GaussianConditional,
  * model/entropy_models.py:313,330,352-353,371-372,393,407-408).  Features are [N, C]
  * row-major; symbol / index / likelihood planes are channel-major [C, N] — the order in

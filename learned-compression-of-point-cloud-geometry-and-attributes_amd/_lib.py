@@ -73,6 +73,12 @@ SIGNATURES = {
     "pcc_conv_wgrad_bf16": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
                                     c_i64, c_void_p]),
     "pcc_chconv": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p]),
+    "pcc_render_scratch_bytes": (c_i64, [c_i32, c_i32]),
+    "pcc_render_view": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
+    "pcc_image_compare_tile": (c_i32, []),
+    "pcc_image_compare_scratch_bytes": (c_i64, [c_i32, c_i32]),
+    "pcc_image_compare": (c_int, [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p]),
     "pcc_octree_scratch_bytes": (c_i64, [c_i64]),
     "pcc_octree_occupancy": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "pcc_octree_expand": (c_int, [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),

@@ -1,0 +1,261 @@
+// View rendering and view PSNR / SSIM for the view-dependent evaluation (evaluate_view_dep.py:102-305).
+//
+// pcc_render_view replaces render_pointviews (evaluate_view_dep.py:308-348: an open3d OpenGL window, which is neither
+// available without a display nor reproducible pixel for pixel) by an exact integer projection of a voxelised cloud: an
+// orthographic z-buffer splat along a signed coordinate axis — every view the reference uses is one
+// (evaluate_view_dep.py:46-57).
+//
+//   u = right . p, v = up . p, d = front . p              (front points from the object to the camera, as open3d's set_front)
+//   the point covers columns (u - u_min) scale + ox + i and rows (v_max - v) scale + oy + j,  i, j in [0, point_size)
+//   pixels outside the image are dropped one by one; the pixel shows the point with the largest d and, among equal d,
+//   the lowest row index; untouched pixels show the background
+//
+// Three kernels: the z-buffer is cleared to 0; one thread per point does point_size^2 64-bit atomicMax of the word
+// ((d + 2^18) << 32) | (0xFFFFFFFF - row); one thread per four pixels resolves the words to colours.  A maximum does not depend
+// on the order its operands arrive in, so the image is bitwise reproducible although the splat is atomic.  |d| <= COORD_LIMIT
+// < 2^18, so d + 2^18 is positive and the word of a drawn pixel is never 0; a row with a coordinate outside the range draws
+// nothing.  Atomic bound: n point_size^2 64-bit atomics on H W words.
+//
+// pcc_image_compare replaces rgb2yuv + peak_signal_noise_ratio + structural_similarity (evaluate_view_dep.py:196-204) by
+// their raw sums in float64: one workgroup per IC_TILE x IC_TILE tile converts the tile and its 6-pixel apron to YUV one
+// channel at a time into LDS, adds the squared differences of the pixels it owns and the SSIM map values of the 7 x 7
+// windows whose top-left pixel it owns, reduces them over a fixed tree and stores its eight partials; a second kernel
+// adds the partials in ascending workgroup order.  No float atomics: the result is bitwise reproducible.  Separate
+// multiplies and adds throughout (the library is built with -ffp-contract=off).
+#include "common.h"
+
+namespace pcc {
+
+constexpr int RENDER_DEPTH_BIAS = 1 << 18;
+constexpr int RENDER_MAX_DIM = 8192;
+
+struct RenderView {
+    int32_t r[3], u[3], f[3];
+    int32_t u_min, v_max, ox, oy, scale, point_size, H, W;
+};
+
+__global__ __launch_bounds__(256) void render_clear_kernel(uint64_t* __restrict__ zbuf, int64_t npix) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < npix) zbuf[i] = 0ull;
+}
+
+__global__ __launch_bounds__(256) void render_splat_kernel(const int32_t* __restrict__ coords, int64_t n, RenderView a,
+                                                           uint64_t* __restrict__ zbuf) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    const int4 c = reinterpret_cast<const int4*>(coords)[row];                  // (batch, x, y, z): the batch is ignored
+    if (!coord_in_range(0, c.y, c.z, c.w)) return;
+    const int u = a.r[0] * c.y + a.r[1] * c.z + a.r[2] * c.w;
+    const int v = a.u[0] * c.y + a.u[1] * c.z + a.u[2] * c.w;
+    const int d = a.f[0] * c.y + a.f[1] * c.z + a.f[2] * c.w;
+    const uint64_t word = ((uint64_t)(uint32_t)(d + RENDER_DEPTH_BIAS) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)row);
+    // 64-bit positions: (u - u_min) * scale stays below 2^19 * 64, but u_min / ox / oy are the caller's
+    const int64_t px0 = ((int64_t)u - a.u_min) * a.scale + a.ox, py0 = ((int64_t)a.v_max - v) * a.scale + a.oy;
+    for (int j = 0; j < a.point_size; ++j) {
+        const int64_t py = py0 + j;
+        if (py < 0 || py >= a.H) continue;
+        for (int i = 0; i < a.point_size; ++i) {
+            const int64_t px = px0 + i;
+            if (px < 0 || px >= a.W) continue;
+            atomicMax(reinterpret_cast<unsigned long long*>(zbuf) + (py * a.W + px), (unsigned long long)word);
+        }
+    }
+}
+
+// four pixels (12 bytes = three aligned words of the image) per thread
+__global__ __launch_bounds__(256) void render_resolve_kernel(const uint64_t* __restrict__ zbuf, const uint8_t* __restrict__ rgb8,
+                                                             uint32_t background, int64_t npix, uint8_t* __restrict__ image) {
+    const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (p0 >= npix) return;
+    uint8_t b[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint64_t word = p0 + k < npix ? zbuf[p0 + k] : 0ull;
+        if (word == 0ull) {
+            b[3 * k] = (uint8_t)background; b[3 * k + 1] = (uint8_t)(background >> 8); b[3 * k + 2] = (uint8_t)(background >> 16);
+        } else {
+            const int64_t row = (int64_t)(0xFFFFFFFFu - (uint32_t)word);
+            b[3 * k] = rgb8[3 * row]; b[3 * k + 1] = rgb8[3 * row + 1]; b[3 * k + 2] = rgb8[3 * row + 2];
+        }
+    }
+    if (p0 + 4 <= npix && (reinterpret_cast<uintptr_t>(image) & 3u) == 0) {
+        uint32_t* out = reinterpret_cast<uint32_t*>(image + 3 * p0);
+#pragma unroll
+        for (int w = 0; w < 3; ++w)
+            out[w] = (uint32_t)b[4 * w] | ((uint32_t)b[4 * w + 1] << 8) | ((uint32_t)b[4 * w + 2] << 16) | ((uint32_t)b[4 * w + 3] << 24);
+    } else {
+        for (int k = 0; k < 12 && p0 * 3 + k < npix * 3; ++k) image[3 * p0 + k] = b[k];
+    }
+}
+
+// ---- image metrics ----
+constexpr int IC_TILE = 32;                   // pixels a workgroup owns per side
+constexpr int IC_WIN = 7;                     // structural_similarity's window
+constexpr int IC_SPAN = IC_TILE + IC_WIN - 1; // the tile and its apron
+constexpr int IC_THREADS = 256;
+
+// scikit-image's yuv_from_rgb
+__device__ const double IC_YUV[3][3] = {{0.299, 0.587, 0.114},
+                                        {-0.14714119, -0.28886916, 0.43601035},
+                                        {0.61497538, -0.51496512, -0.10001026}};
+
+__device__ __forceinline__ double ic_yuv(const uint8_t* __restrict__ px, int ch) {
+    const double r = (double)px[0] / 255.0, g = (double)px[1] / 255.0, b = (double)px[2] / 255.0;
+    return (r * IC_YUV[ch][0] + g * IC_YUV[ch][1]) + b * IC_YUV[ch][2];
+}
+
+// sum / min / max of one value per thread over the workgroup, as a fixed tree in LDS (op: 0 sum, 1 min, 2 max)
+__device__ __forceinline__ double ic_block_reduce(double v, int op, double* red) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    red[t] = v;
+    __syncthreads();
+    for (int s = IC_THREADS / 2; s > 0; s >>= 1) {
+        if (t < s) {
+            const double a = red[t], b = red[t + s];
+            red[t] = op == 0 ? a + b : (op == 1 ? (b < a ? b : a) : (b > a ? b : a));
+        }
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ __launch_bounds__(IC_THREADS) void image_compare_tile_kernel(const uint8_t* __restrict__ ref, const uint8_t* __restrict__ img,
+                                                                        int H, int W, int tiles_x, double* __restrict__ partials) {
+    __shared__ double xs[IC_SPAN][IC_SPAN], ys[IC_SPAN][IC_SPAN];
+    __shared__ double red[IC_THREADS];
+    const int t = threadIdx.x;
+    const int r0 = (blockIdx.x / tiles_x) * IC_TILE, c0 = (blockIdx.x % tiles_x) * IC_TILE;
+    const double C1 = 1e-4, C2 = 9e-4, cov_norm = 49.0 / 48.0;
+    double sse[3] = {0.0, 0.0, 0.0}, ssim[3] = {0.0, 0.0, 0.0};
+    double lo = INFINITY, hi = -INFINITY;
+    for (int ch = 0; ch < 3; ++ch) {
+        __syncthreads();                                   // the previous channel's windows are read
+        for (int e = t; e < IC_SPAN * IC_SPAN; e += IC_THREADS) {
+            const int lr = e / IC_SPAN, lc = e % IC_SPAN;
+            const int r = r0 + lr, c = c0 + lc;
+            double x = 0.0, y = 0.0;                       // outside the image: read by no window that counts
+            if (r < H && c < W) {
+                const int64_t at = 3 * ((int64_t)r * W + c);
+                x = ic_yuv(ref + at, ch);
+                y = ic_yuv(img + at, ch);
+                if (lr < IC_TILE && lc < IC_TILE) {        // a pixel this workgroup owns
+                    const double diff = x - y;
+                    sse[ch] = sse[ch] + diff * diff;
+                    lo = x < lo ? x : lo;
+                    hi = x > hi ? x : hi;
+                }
+            }
+            xs[lr][lc] = x;
+            ys[lr][lc] = y;
+        }
+        __syncthreads();
+        for (int o = t; o < IC_TILE * IC_TILE; o += IC_THREADS) {
+            const int lr = o / IC_TILE, lc = o % IC_TILE;
+            if (r0 + lr + IC_WIN > H || c0 + lc + IC_WIN > W) continue;      // the window leaves the image: not in the crop
+            double sx = 0.0, sy = 0.0, sxx = 0.0, syy = 0.0, sxy = 0.0;
+            for (int j = 0; j < IC_WIN; ++j) {
+#pragma unroll
+                for (int i = 0; i < IC_WIN; ++i) {
+                    const double x = xs[lr + j][lc + i], y = ys[lr + j][lc + i];
+                    sx = sx + x; sy = sy + y;
+                    sxx = sxx + x * x; syy = syy + y * y; sxy = sxy + x * y;
+                }
+            }
+            const double ux = sx / 49.0, uy = sy / 49.0, uxx = sxx / 49.0, uyy = syy / 49.0, uxy = sxy / 49.0;
+            const double vx = cov_norm * (uxx - ux * ux), vy = cov_norm * (uyy - uy * uy), vxy = cov_norm * (uxy - ux * uy);
+            const double S = ((2.0 * ux * uy + C1) * (2.0 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
+            ssim[ch] = ssim[ch] + S;
+        }
+    }
+    double out[8];
+    for (int ch = 0; ch < 3; ++ch) out[ch] = ic_block_reduce(sse[ch], 0, red);
+    for (int ch = 0; ch < 3; ++ch) out[3 + ch] = ic_block_reduce(ssim[ch], 0, red);
+    out[6] = ic_block_reduce(lo, 1, red);
+    out[7] = ic_block_reduce(hi, 2, red);
+    if (t < 8) partials[8 * (int64_t)blockIdx.x + t] = out[t];
+}
+
+// thread q adds (or takes the minimum / maximum of) quantity q of every workgroup, in ascending workgroup order
+__global__ __launch_bounds__(64) void image_compare_sum_kernel(const double* __restrict__ partials, int tiles, double* __restrict__ out) {
+    const int q = threadIdx.x;
+    if (q >= 8) return;
+    double acc = partials[q];
+    for (int b = 1; b < tiles; ++b) {
+        const double v = partials[8 * (int64_t)b + q];
+        acc = q < 6 ? acc + v : (q == 6 ? (v < acc ? v : acc) : (v > acc ? v : acc));
+    }
+    out[q] = acc;
+}
+
+static bool signed_unit_axis(const int32_t* a) {
+    const int nz = (a[0] != 0) + (a[1] != 0) + (a[2] != 0);
+    return nz == 1 && a[0] * a[0] + a[1] * a[1] + a[2] * a[2] == 1;
+}
+static int dot3(const int32_t* a, const int32_t* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+
+}  // namespace pcc
+
+using namespace pcc;
+
+extern "C" {
+
+int64_t pcc_render_scratch_bytes(int32_t H, int32_t W) {
+    if (H < 1 || W < 1 || H > RENDER_MAX_DIM || W > RENDER_MAX_DIM) return 0;
+    return (int64_t)H * W * 8;
+}
+
+int pcc_render_view(const int32_t* coords, const uint8_t* rgb8, int64_t n, const int32_t* right, const int32_t* up, const int32_t* front,
+                    int32_t u_min, int32_t v_max, int32_t ox, int32_t oy, int32_t scale, int32_t point_size, int32_t H, int32_t W,
+                    const uint8_t* background, void* scratch, int64_t scratch_bytes, uint8_t* image, void* stream) {
+    PCC_REQUIRE(right && up && front && background, "pcc_render_view: axes and background required");
+    PCC_REQUIRE(signed_unit_axis(right) && signed_unit_axis(up) && signed_unit_axis(front),
+                "pcc_render_view: right, up and front must be signed unit coordinate axes");
+    PCC_REQUIRE(dot3(right, up) == 0 && dot3(up, front) == 0 && dot3(right, front) == 0, "pcc_render_view: axes must be mutually orthogonal");
+    const int32_t cross[3] = {up[1] * front[2] - up[2] * front[1], up[2] * front[0] - up[0] * front[2], up[0] * front[1] - up[1] * front[0]};
+    PCC_REQUIRE(cross[0] == right[0] && cross[1] == right[1] && cross[2] == right[2], "pcc_render_view: right must be up x front");
+    PCC_REQUIRE(scale >= 1 && scale <= 64, "pcc_render_view: scale must be 1 .. 64 (got %d)", scale);
+    PCC_REQUIRE(point_size >= 1 && point_size <= 16, "pcc_render_view: point_size must be 1 .. 16 (got %d)", point_size);
+    PCC_REQUIRE(H >= 1 && H <= RENDER_MAX_DIM && W >= 1 && W <= RENDER_MAX_DIM, "pcc_render_view: H and W must be 1 .. %d (got %d x %d)",
+                RENDER_MAX_DIM, H, W);
+    PCC_REQUIRE(n >= 0 && n <= 0xFFFFFFFEll, "pcc_render_view: 0 .. 2^32 - 2 points");
+    PCC_REQUIRE(n == 0 || (coords && rgb8), "pcc_render_view: null cloud with n > 0");
+    PCC_REQUIRE(scratch && image, "pcc_render_view: z-buffer and image required");
+    PCC_REQUIRE(scratch_bytes >= pcc_render_scratch_bytes(H, W), "pcc_render_view: scratch too small");
+    RenderView a;
+    for (int k = 0; k < 3; ++k) { a.r[k] = right[k]; a.u[k] = up[k]; a.f[k] = front[k]; }
+    a.u_min = u_min; a.v_max = v_max; a.ox = ox; a.oy = oy; a.scale = scale; a.point_size = point_size; a.H = H; a.W = W;
+    const int64_t npix = (int64_t)H * W;
+    const uint32_t bg = (uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16);
+    hipStream_t st = as_stream(stream);
+    uint64_t* zbuf = reinterpret_cast<uint64_t*>(scratch);
+    hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
+    if (n > 0) hipLaunchKernelGGL(render_splat_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
+    hipLaunchKernelGGL(render_resolve_kernel, dim3(blocks_for((npix + 3) / 4, 256)), dim3(256), 0, st, zbuf, rgb8, bg, npix, image);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+int32_t pcc_image_compare_tile(void) { return IC_TILE; }
+
+int64_t pcc_image_compare_scratch_bytes(int32_t H, int32_t W) {
+    if (H < IC_WIN || W < IC_WIN || H > RENDER_MAX_DIM || W > RENDER_MAX_DIM) return 0;
+    return (int64_t)((H + IC_TILE - 1) / IC_TILE) * ((W + IC_TILE - 1) / IC_TILE) * 8 * (int64_t)sizeof(double);
+}
+
+int pcc_image_compare(const uint8_t* ref, const uint8_t* img, int32_t H, int32_t W, void* scratch, int64_t scratch_bytes, double* out,
+                      void* stream) {
+    PCC_REQUIRE(H >= IC_WIN && W >= IC_WIN, "pcc_image_compare: images must be at least 7 x 7 (got %d x %d)", H, W);
+    PCC_REQUIRE(H <= RENDER_MAX_DIM && W <= RENDER_MAX_DIM, "pcc_image_compare: H and W must be at most %d (got %d x %d)", RENDER_MAX_DIM, H, W);
+    PCC_REQUIRE(ref && img && scratch && out, "pcc_image_compare: null pointer");
+    PCC_REQUIRE(scratch_bytes >= pcc_image_compare_scratch_bytes(H, W), "pcc_image_compare: scratch too small");
+    const int tiles_x = (W + IC_TILE - 1) / IC_TILE, tiles = tiles_x * ((H + IC_TILE - 1) / IC_TILE);
+    hipStream_t st = as_stream(stream);
+    double* partials = reinterpret_cast<double*>(scratch);
+    hipLaunchKernelGGL(image_compare_tile_kernel, dim3(tiles), dim3(IC_THREADS), 0, st, ref, img, H, W, tiles_x, partials);
+    hipLaunchKernelGGL(image_compare_sum_kernel, dim3(1), dim3(64), 0, st, partials, tiles, out);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+}  // extern "C"

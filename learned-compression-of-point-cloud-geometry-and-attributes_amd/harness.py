@@ -5,6 +5,10 @@ evaluate.py:55-216), plus the quality numbers the sweep records.
 Differences in form only: clouds are ``[N, 6]`` GPU tensors instead of open3d objects, and the
 metrics come from metrics.PointCloudMetric on the GPU instead of the external ``pc_error`` binary
 (utils.py:206-290) — same quantities (D1 / Y / U / V PSNR, symmetric = worse direction).
+
+``evaluate_view_dependent`` mirrors the rows of evaluate_view_dep.py:139-301: one frame coded with a uniform, a
+view-dependent and a region-of-interest quality map, each judged by rendering a fixed view (render.render_view instead
+of an open3d window) and comparing it with the source's view in YUV (render.view_metrics instead of scikit-image).
 """
 import os
 import time
@@ -12,6 +16,8 @@ import time
 import numpy as np
 import torch
 
+from . import render
+from .io import write_png
 from .metrics import PointCloudMetric
 from .sparse import SparseTensor
 
@@ -63,3 +69,67 @@ def evaluate_frame(experiment, model, data, q_a, q_g, device, base_path, resolut
             "n_source": int(src.shape[0]), "n_decoded": int(rec.shape[0]),
             "sym_p2p_psnr": res["sym_psnr_mse"], "sym_y_psnr": res["sym_y_psnr"], "sym_u_psnr": res["sym_u_psnr"],
             "sym_v_psnr": res["sym_v_psnr"]}
+
+
+def _extent(points, axis):
+    c = points[:, axis]
+    return float(c.min()), float(c.max())
+
+
+def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path, view="front", H=1024, W=512, gradient=None, roi=None,
+                            save_images=False, details=None):
+    """The three rows of evaluate_view_dep.py:139-301 for one frame -> {"uniform": row, "view": row, "roi": row}, each row
+    {"bpp", "q_a", "q_g", "key", "psnr", "ssim"}.
+
+    ``view``: a preset of render.VIEWS or a (front, up) pair.  ``gradient=(axis, lo, hi)``: the view-dependent map, score =
+    clip((p[axis] - lo) / (hi - lo), 0, 1) with axis 0..2 over x, y, z (:209-215; lo > hi makes quality rise towards
+    smaller coordinates); ``roi=(axis, plane)``: score = 1 where p[axis] >= plane, else 0 (:254-260).  Both maps scale
+    (q_g, q_a) per point.  The reference keeps these numbers per sequence (:58-77); they stay with the caller.  None
+    derives them from the frame: the gradient runs along the viewing axis from the farthest voxel (0) to the nearest (1),
+    the region of interest is the half of the frame towards the view's right.
+
+    All four images (the source and the three reconstructions) are rendered in the SOURCE's frame.  ``save_images`` writes
+    them as PNG under ``<base_path>/<experiment>/renders_view/`` (the reference's names, :188-278).  ``details`` (a dict)
+    receives ``{"source" | "uniform" | "view" | "roi": (cloud, image)}`` for callers that want the tensors."""
+    front, up = render._view(view)
+    right, up, front = render.view_axes(front, up)
+    tag = view if isinstance(view, str) else "custom"
+    points = data["src"]["points"][0].to(device, dtype=torch.float)
+    if gradient is None:
+        axis = [abs(a) for a in front].index(1)
+        lo, hi = _extent(points, axis)
+        gradient = (axis, lo, hi) if front[axis] > 0 else (axis, hi, lo)
+    if roi is None:
+        axis = [abs(a) for a in right].index(1)
+        lo, hi = _extent(points, axis)
+        roi = (axis, (lo + hi) / 2.0)
+    g_axis, g_lo, g_hi = gradient
+    r_axis, r_plane = roi
+    maps = {
+        "uniform": None,
+        "view": torch.clamp((points[:, g_axis] - float(g_lo)) / (float(g_hi) - float(g_lo)), 0, 1),
+        "roi": (points[:, r_axis] >= float(r_plane)).to(torch.float),
+    }
+    img_dir = os.path.join(base_path, experiment, "renders_view")
+    if save_images:
+        os.makedirs(img_dir, exist_ok=True)
+    rows, frame, ref_img = {}, None, None
+    for key, score in maps.items():
+        qa = q_a if score is None else (float(q_a) * score).reshape(-1, 1)
+        qg = q_g if score is None else (float(q_g) * score).reshape(-1, 1)
+        src, rec, bpp, _, _ = compress_model_ours(experiment, model, data, qa, qg, device, base_path)
+        if ref_img is None:
+            frame = render.view_frame(src, front, up, H, W)
+            ref_img = render.render_view(src, front, up, H, W, frame=frame)
+            if save_images:
+                write_png(os.path.join(img_dir, "ref_%s.png" % tag), ref_img)
+            if details is not None:
+                details["source"] = (src, ref_img)
+        img = render.render_view(rec, front, up, H, W, frame=frame)
+        m = render.view_metrics(ref_img, img)
+        rows[key] = {"bpp": bpp, "q_a": q_a, "q_g": q_g, "key": key, "psnr": m["psnr"], "ssim": m["ssim"]}
+        if save_images:
+            write_png(os.path.join(img_dir, "%s_a%s_g%s_%s.png" % (key, str(q_a), str(q_g), tag)), img)
+        if details is not None:
+            details[key] = (rec, img)
+    return rows

@@ -7,7 +7,13 @@ open3d is not available here.  Supported: ``format ascii 1.0`` and ``format bina
 optionally, red / green / blue (uchar) — any further properties (normals, alpha, ...) are skipped.
 A cloud is a float32 ``[N, 6]`` array: voxel coordinates and rgb in [0, 1] — the layout
 ``ColorModel.compress`` takes (model/model.py:95-123).
+
+``write_png`` writes the rendered views of the view-dependent evaluation (evaluate_view_dep.py:346,
+``capture_screen_image``) with the standard library alone: no imaging package is assumed.
 """
+import struct
+import zlib
+
 import numpy as np
 
 _TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
@@ -105,3 +111,22 @@ def write_ply(path, cloud, binary=True):
                 if has_rgb:
                     row += " %d %d %d" % (rgb[i, 0], rgb[i, 1], rgb[i, 2])
                 f.write((row + "\n").encode("ascii"))
+
+
+def write_png(path, img):
+    """img: uint8 [H, W, 3] (array or tensor) -> an 8-bit RGB PNG, non-interlaced, every scanline with filter type 0."""
+    if hasattr(img, "detach"):
+        img = img.detach().cpu().numpy()
+    a = np.ascontiguousarray(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("write_png: an image is a uint8 [H, W, 3] array")
+    h, w = a.shape[:2]
+    rows = np.zeros((h, 1 + 3 * w), dtype=np.uint8)          # a filter byte (0 = none) in front of every scanline
+    rows[:, 1:] = a.reshape(h, 3 * w)
+
+    def chunk(tag, body):
+        return struct.pack(">I", len(body)) + tag + body + struct.pack(">I", zlib.crc32(tag + body) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
+                + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))

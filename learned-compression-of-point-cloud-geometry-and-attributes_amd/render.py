@@ -1,0 +1,204 @@
+"""View rendering and view PSNR / SSIM: the evaluation half of the view-dependent and region-of-interest experiment
+(the reference's evaluate_view_dep.py:102-305: ``render_pointviews``, then ``rgb2yuv``, ``peak_signal_noise_ratio`` and
+``structural_similarity`` on the rendered images).
+
+The reference renders through open3d's OpenGL window (evaluate_view_dep.py:308-348), which needs a display and is not
+reproducible pixel for pixel.  Every view it uses is a signed coordinate axis (evaluate_view_dep.py:46-57), so the
+renderer here is an exact integer projection of a voxelised cloud — an orthographic z-buffer splat (csrc/render.hip,
+``pcc_render_view``) — the same move metrics.py makes for the KD-tree:
+
+    u = right . p,  v = up . p,  d = front . p          (front points from the object to the camera: open3d's set_front)
+    a point covers columns (u - u_min) * scale + ox + i and rows (v_max - v) * scale + oy + j,  i, j in [0, point_size)
+
+A pixel shows the point with the largest d; among equal d the lowest row wins, and rows are put in canonical (x, y, z)
+order before the call, so for a duplicate-free cloud the tie goes to the smaller (x, y, z) whatever the input order.
+What differs from open3d: no perspective (the reference narrows the field of view to its minimum, :340, which is close to
+orthographic), square integer splats instead of round anti-aliased GL points, an integer ``scale`` in place of ``zoom``.
+
+``view_metrics`` restates scikit-image's formulas in float64 (``pcc_image_compare``).  scikit-image is no dependency of
+this project and was not at hand: the ``yuv_from_rgb`` coefficients, the SSIM constants (K1 = 0.01, K2 = 0.03, 7 x 7
+uniform window, sample covariance, crop of 3) and the data-range rule of ``peak_signal_noise_ratio`` are recalled from its
+source, not pinned against it.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, ptr
+
+# named views as data, (front, up): evaluate_view_dep.py:49-50 (the 8iVFB bodies) and :54-55 (MVUB)
+VIEWS = {"front": ((0, 0, 1), (0, 1, 0)), "side": ((-1, 0, 0), (0, 1, 0))}
+VIEWS_MVUB = {"front": ((0, -1, 0), (0, 0, 1)), "side": ((-1, 0, 0), (0, 0, 1))}
+
+COORD_LIMIT = 130000          # PCC_COORD_LIMIT (include/pcc_hip.h)
+
+
+def _axis(v, name):
+    try:
+        a = [int(x) for x in v]
+        exact = len(a) == 3 and all(float(x) == float(y) for x, y in zip(a, v))
+    except (TypeError, ValueError):
+        exact = False
+    if not exact or sorted(abs(x) for x in a) != [0, 0, 1]:
+        raise ValueError("%s must be a signed unit coordinate axis such as (0, 0, 1) or (-1, 0, 0), got %r" % (name, v))
+    return tuple(a)
+
+
+def view_axes(front, up):
+    """-> (right, up, front) as integer triples, right = up x front.  ValueError unless front and up are orthogonal signed
+    coordinate axes."""
+    f, u = _axis(front, "front"), _axis(up, "up")
+    if sum(a * b for a, b in zip(f, u)) != 0:
+        raise ValueError("front %r and up %r are not orthogonal" % (front, up))
+    r = (u[1] * f[2] - u[2] * f[1], u[2] * f[0] - u[0] * f[2], u[0] * f[1] - u[1] * f[0])
+    return r, u, f
+
+
+def _view(view):
+    """a preset name or a (front, up) pair -> (front, up)"""
+    if isinstance(view, str):
+        if view not in VIEWS:
+            raise ValueError("unknown view %r: one of %s or a (front, up) pair" % (view, sorted(VIEWS)))
+        return VIEWS[view]
+    front, up = view
+    return front, up
+
+
+def _int_xyz(cloud):
+    """[N, >= 3] tensor or array -> its xyz columns as an int32 tensor (on the cloud's device); ValueError unless integers"""
+    if not torch.is_tensor(cloud):
+        cloud = torch.as_tensor(np.asarray(cloud))
+    if cloud.dim() != 2 or cloud.shape[1] < 3:
+        raise ValueError("a cloud is a [N, 6] array: x, y, z, r, g, b")
+    xyz = cloud[:, :3]
+    ixyz = torch.round(xyz.double()).to(torch.int32)
+    if not torch.equal(ixyz.to(xyz.dtype), xyz):
+        raise ValueError("views are rendered from voxelised clouds: coordinates must be integers")
+    return cloud, ixyz
+
+
+def view_frame(cloud, front, up, H, W, scale=None):
+    """The framing (u_min, u_max, v_min, v_max, scale, ox, oy) that centres ``cloud``'s bounding box in an H x W image:
+    ox = (W - (u_max - u_min + 1) * scale) // 2, oy likewise with v and H.  ``scale=None`` picks the largest integer scale at
+    which the box fits, at least 1.  An empty cloud is framed like the single voxel (0, 0, 0)."""
+    r, u, _ = view_axes(front, up)
+    _, xyz = _int_xyz(cloud)
+    if xyz.shape[0] == 0:
+        u_min = u_max = v_min = v_max = 0
+    else:
+        lo, hi = xyz.amin(dim=0).tolist(), xyz.amax(dim=0).tolist()
+
+        def span(axis):                       # a signed unit axis picks one coordinate, possibly negated
+            k = [abs(a) for a in axis].index(1)
+            return (lo[k], hi[k]) if axis[k] > 0 else (-hi[k], -lo[k])
+
+        (u_min, u_max), (v_min, v_max) = span(r), span(u)
+    wu, wv = u_max - u_min + 1, v_max - v_min + 1
+    if scale is None:
+        scale = max(1, min(int(W) // wu, int(H) // wv))
+    scale = int(scale)
+    return u_min, u_max, v_min, v_max, scale, (int(W) - wu * scale) // 2, (int(H) - wv * scale) // 2
+
+
+def colours_to_bytes(rgb):
+    """clamp(rint(float32(c) * 255), 0, 255) as uint8"""
+    return torch.clamp(torch.round(rgb.to(torch.float32) * 255.0), 0.0, 255.0).to(torch.uint8)
+
+
+def render_view(cloud, front, up, H, W, frame=None, point_size=None, background=(255, 255, 255), device=None):
+    """Render ``cloud`` ([N, 6]: integer x, y, z and r, g, b in [0, 1]; one batch item) from the signed axis ``front`` with
+    ``up`` upwards -> uint8 [H, W, 3] tensor on the cloud's device (``device`` for an array; a GPU: there is no CPU renderer).
+
+    ``frame``: a ``view_frame`` result (of this or of another cloud — reconstructions are rendered in their source's
+    frame); None frames the cloud itself.  ``point_size=None`` means the frame's scale: adjacent voxels tile the image
+    without gaps or overlap."""
+    L = _lib.lib()
+    r, u, f = view_axes(front, up)
+    cloud, xyz = _int_xyz(cloud)
+    if cloud.shape[1] < 6:
+        raise ValueError("a cloud is a [N, 6] array: x, y, z, r, g, b")
+    dev = torch.device(device) if device is not None else (cloud.device if cloud.is_cuda else torch.device("cuda:0"))
+    if dev.type != "cuda":
+        raise ValueError("render_view runs on the GPU: got device %s" % dev)
+    n = int(cloud.shape[0])
+    if n and int(xyz.abs().max()) > COORD_LIMIT:
+        raise ValueError("render_view: coordinates beyond +-%d" % COORD_LIMIT)
+    if frame is None:
+        frame = view_frame(xyz, f, u, H, W)
+    u_min, _, _, v_max, scale, ox, oy = (int(v) for v in frame)
+    point_size = scale if point_size is None else int(point_size)
+    bg = np.asarray(background)
+    if bg.shape != (3,) or bg.min() < 0 or bg.max() > 255:
+        raise ValueError("background is three bytes")
+    bg = bg.astype(np.uint8)
+    with torch.cuda.device(dev):
+        coords = torch.cat([torch.zeros((n, 1), dtype=torch.int32, device=dev), xyz.to(dev)], dim=1).contiguous()
+        rgb8 = colours_to_bytes(cloud[:, 3:6].to(dev)).contiguous()
+        if n > 1:                                      # canonical (x, y, z) order: the tie rule's "lowest row"
+            nbytes = L.pcc_sort_scratch_bytes(n)
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            perm = torch.empty(n, dtype=torch.int32, device=dev)
+            check(L.pcc_sort_coords(ptr(coords), n, ptr(perm), ptr(scratch), nbytes, _lib.stream()))
+            perm = perm.long()
+            coords, rgb8 = coords[perm].contiguous(), rgb8[perm].contiguous()
+        zbytes = L.pcc_render_scratch_bytes(int(H), int(W))
+        zbuf = torch.empty(max(zbytes, 8), dtype=torch.uint8, device=dev)
+        image = torch.empty((int(H), int(W), 3), dtype=torch.uint8, device=dev) if zbytes else None
+        axes = [np.asarray(a, dtype=np.int32) for a in (r, u, f)]
+        check(L.pcc_render_view(ptr(coords) if n else None, ptr(rgb8) if n else None, n, ptr(axes[0]), ptr(axes[1]), ptr(axes[2]),
+                                u_min, v_max, ox, oy, scale, point_size, int(H), int(W), ptr(bg), ptr(zbuf), zbytes, ptr(image),
+                                _lib.stream()))
+    return image
+
+
+def data_range_of(ref_min):
+    """scikit-image's rule for float images when ``peak_signal_noise_ratio`` is given no data_range: 1 if the reference
+    image's smallest value is >= 0, else 2 (the range of [-1, 1]) — what evaluate_view_dep.py:203 gets, since U and V are
+    signed"""
+    return 1.0 if ref_min >= 0 else 2.0
+
+
+def image_compare(ref_img, img):
+    """The raw sums of ``pcc_image_compare`` for two uint8 [H, W, 3] GPU images -> eight floats: per-channel (Y, U, V) sums
+    of squared differences, per-channel sums of the SSIM map over its (H - 6) x (W - 6) crop, smallest and largest YUV value
+    of ``ref_img``.  Bitwise reproducible."""
+    L = _lib.lib()
+    if not (torch.is_tensor(ref_img) and torch.is_tensor(img)):
+        raise ValueError("image_compare: images are uint8 [H, W, 3] tensors on the GPU")
+    if ref_img.dtype != torch.uint8 or img.dtype != torch.uint8 or ref_img.dim() != 3 or ref_img.shape[2] != 3 or ref_img.shape != img.shape:
+        raise ValueError("image_compare: two uint8 [H, W, 3] images of one size")
+    if not ref_img.is_cuda:
+        raise ValueError("image_compare runs on the GPU: got device %s" % ref_img.device)
+    dev = ref_img.device
+    H, W = int(ref_img.shape[0]), int(ref_img.shape[1])
+    with torch.cuda.device(dev):
+        a, b = ref_img.contiguous(), img.to(dev).contiguous()
+        nbytes = L.pcc_image_compare_scratch_bytes(H, W)
+        scratch = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+        out = torch.empty(8, dtype=torch.float64, device=dev)
+        check(L.pcc_image_compare(ptr(a), ptr(b), H, W, ptr(scratch), nbytes, ptr(out), _lib.stream()))
+        return out.tolist()
+
+
+def metrics_from_sums(sums, H, W, data_range=None):
+    """the numbers of ``view_metrics`` from the eight raw sums of an H x W pair"""
+    n = float(H * W)
+    y_mse, u_mse, v_mse = (s / n for s in sums[0:3])
+    mse = (sums[0] + sums[1] + sums[2]) / (3.0 * n)
+    if data_range is None:
+        data_range = data_range_of(sums[6])
+    crop = float((H - 6) * (W - 6))
+    ssim = (sums[3] / crop + sums[4] / crop + sums[5] / crop) / 3.0
+    psnr = math.inf if mse <= 0 else 10.0 * math.log10(float(data_range) ** 2 / mse)
+    return {"psnr": psnr, "ssim": ssim, "y_mse": y_mse, "u_mse": u_mse, "v_mse": v_mse}
+
+
+def view_metrics(ref_img, img, data_range=None):
+    """PSNR and SSIM of a rendered view against the reference view, in YUV as evaluate_view_dep.py:196-204 takes them ->
+    {"psnr", "ssim", "y_mse", "u_mse", "v_mse"}.  PSNR = 10 log10(data_range^2 / mse), mse over all 3 H W values (inf at 0);
+    ``data_range=None`` follows ``data_range_of``.  SSIM is the mean of the three channels' mean SSIM
+    (structural_similarity(channel_axis=2, data_range=1.0), 7 x 7 uniform window)."""
+    sums = image_compare(ref_img, img)
+    return metrics_from_sums(sums, int(ref_img.shape[0]), int(ref_img.shape[1]), data_range)

@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""The view-dependent / region-of-interest experiment of the reference's evaluate_view_dep.py on one frame: the frame is coded
+with a uniform, a view-dependent and a region-of-interest quality map (harness.evaluate_view_dependent), every
+reconstruction is rendered from a fixed view in the source's frame and compared with the source's view in YUV.  Writes
+<out>/<experiment>/view_dep.csv (the reference's table, :303-305) and the four PNGs under <out>/<experiment>/renders_view/.
+
+The frame is a PLY path or a synthetic shell ("config1", "config2", or --grid / --radius).  Seeded random weights unless
+--weights is given: their rates and qualities exercise the pipeline, they are not codec quality.  The gradient and cut-off
+numbers the reference keeps per sequence (:58-77) are arguments here; left out, they follow the frame's extent.
+
+usage: view_dep.py [config1 | config2 | frame.ply] [--out DIR] [--view front|side] [--height 1024] [--width 512]
+                   [--q-g 0.4] [--q-a 0.8] [--gradient AXIS LO HI] [--roi AXIS PLANE] [--weights W.pt] [--repeat N]"""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+import pcc_amd  # noqa: E402,F401
+from pcc_amd import io, render, synthetic as syn  # noqa: E402
+from pcc_amd.harness import evaluate_view_dependent  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("frame", nargs="?", default="config1")
+    ap.add_argument("--out", default=os.path.join(ROOT, "job_out", "view_dep"))
+    ap.add_argument("--experiment", default="seeded")
+    ap.add_argument("--view", default="front", choices=sorted(render.VIEWS))
+    ap.add_argument("--mvub", action="store_true", help="the MVUB pair of views (up = +z) instead of the 8iVFB pair")
+    ap.add_argument("--height", type=int, default=1024)
+    ap.add_argument("--width", type=int, default=512)
+    ap.add_argument("--q-g", type=float, default=0.4)
+    ap.add_argument("--q-a", type=float, default=0.8)
+    ap.add_argument("--gradient", nargs=3, type=float, metavar=("AXIS", "LO", "HI"))
+    ap.add_argument("--roi", nargs=2, type=float, metavar=("AXIS", "PLANE"))
+    ap.add_argument("--grid", type=int)
+    ap.add_argument("--radius", type=float)
+    ap.add_argument("--weights")
+    ap.add_argument("--repeat", type=int, default=0, help="time render_view and view_metrics over N further calls")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args()
+
+    if a.frame.lower().endswith(".ply"):
+        pts = io.read_ply(a.frame)
+    elif a.grid:
+        pts = syn.sphere_shell(grid=a.grid, radius=a.radius or 0.25 * a.grid, half_width=0.5)
+    else:
+        pts = syn.sphere_shell(**{"config1": syn.CONFIG1, "config2": syn.CONFIG2}[a.frame])
+    dev = a.device
+    model = syn.make_model(seed=0, device=dev)
+    if a.weights:
+        model.load_state_dict(torch.load(a.weights, map_location=dev))
+    model.update()
+    data = {"src": {"points": torch.from_numpy(pts[None, :, :3]), "colors": torch.from_numpy(pts[None, :, 3:])}}
+    view = (render.VIEWS_MVUB if a.mvub else render.VIEWS)[a.view]
+    gradient = None if a.gradient is None else (int(a.gradient[0]), a.gradient[1], a.gradient[2])
+    roi = None if a.roi is None else (int(a.roi[0]), a.roi[1])
+    details = {}
+    t0 = time.time()
+    rows = evaluate_view_dependent(a.experiment, model, data, a.q_a, a.q_g, dev, a.out, view=view if a.mvub else a.view, H=a.height,
+                                   W=a.width, gradient=gradient, roi=roi, save_images=True, details=details)
+    t_all = time.time() - t0
+    path = os.path.join(a.out, a.experiment, "view_dep.csv")
+    with open(path, "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["bpp", "q_a", "q_g", "key", "psnr", "ssim"])
+        w.writeheader()
+        for row in rows.values():
+            w.writerow(row)
+    for key, row in rows.items():
+        print("%-8s bpp %.4f  view psnr %.3f dB  view ssim %.5f" % (key, row["bpp"], row["psnr"], row["ssim"]))
+    result = {"frame": a.frame, "n_points": int(pts.shape[0]), "H": a.height, "W": a.width, "view": a.view, "t_three_rows_s": t_all}
+    if a.repeat > 0:
+        src, ref_img = details["source"]
+        rec, img = details["uniform"]
+        front, up = view
+        frame = render.view_frame(src, front, up, a.height, a.width)
+
+        def timed(fn):
+            fn()
+            torch.cuda.synchronize()
+            t = time.time()
+            for _ in range(a.repeat):
+                fn()
+            torch.cuda.synchronize()
+            return (time.time() - t) / a.repeat * 1e3
+
+        result["render_view_ms"] = timed(lambda: render.render_view(rec, front, up, a.height, a.width, frame=frame))
+        result["view_metrics_ms"] = timed(lambda: render.view_metrics(ref_img, img))
+        result["scale"] = frame[4]
+    print(json.dumps(result))
+    print("wrote", path)
+
+
+if __name__ == "__main__":
+    main()
