@@ -101,6 +101,53 @@ int pcc_children(const int32_t* coords, int64_t n, int32_t ts, int32_t ksize, ui
                  int32_t* vals, int64_t cap, int32_t* scratch, int32_t* out_coords,
                  int64_t* out_count, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Training augmentation (data/transform.py of the reference; every configuration applies both,
+ * configs/Ours.yaml:29-35).
+ * ------------------------------------------------------------------------------------- */
+/* RandomRotate (data/transform.py:425-494) for a whole collated batch: every row is rotated about the
+ * block centre by the matrix of its batch item, rounded to the voxel grid, and duplicates are dropped.
+ * rot: float32 [nbatch,9], row-major 3x3 per item; half = block_size / 2.  The arithmetic is exact fp32,
+ * every product and sum rounded separately (numpy float32 reproduces it bit for bit):
+ *     d = (float)c - half                                  per axis
+ *     x' = ((d_x R00 + d_y R01) + d_z R02) + half          rows 1 and 2 of R alike for y', z'
+ *     rintf (ties to even), then the conversion to int32;  the batch index passes through
+ * which is the sum order of torch.mm(points - s/2, R.T) + s/2.  With the identity matrix integer
+ * coordinates pass through unchanged.  Candidates that land on the same (batch, x, y, z) keep the lowest
+ * input row; output rows come in input order of the winners, so a collated batch stays grouped by item,
+ * and equal xyz in two items never merge.  out_coords: int32 [n,4]; out_src: int32 [n], out_src[r] = the
+ * input row that produced output row r; *out_count (device int64): the number of output rows, or
+ * PCC_COUNT_ERR_RANGE when a result is not finite or lies beyond PCC_COORD_LIMIT or a batch index is not
+ * in 0 .. nbatch-1 (such a value is never converted to an integer).  scratch: int32
+ * [pcc_scan_scratch_elems(n)].  On return (keys, vals, cap) is the hash table of the OUTPUT set with
+ * tensor stride 1, as for pcc_stride_map (cap >= pcc_hash_capacity(n)).
+ * The reference removes NO duplicates (its first_occurrence_indices is the inverse map again, so it
+ * returns N rows gathered from the first U); this is what its docstring says it does. */
+int pcc_augment_rotate(const int32_t* coords, int64_t n, const float* rot, int32_t nbatch, float half,
+                       uint64_t* keys, int32_t* vals, int64_t cap, int32_t* scratch, int32_t* out_coords,
+                       int32_t* out_src, int64_t* out_count, void* stream);
+
+/* ColorJitter (data/transform.py:107-130: torchvision.transforms.ColorJitter on float colours in [0,1]),
+ * per batch item.  rgb, out: float32 [n,3]; offsets: DEVICE int64 [nbatch+1], item i owns rows
+ * offsets[i] .. offsets[i+1]-1 (contiguous, ascending; an empty item is legal); params: float32 [nbatch,4]
+ * = (brightness, contrast, saturation, hue) factors; order: int32 [nbatch,4], the order in which the four
+ * operations (0 brightness, 1 contrast, 2 saturation, 3 hue) are applied to the item.
+ *     gray(c) = 0.2989 r + 0.587 g + 0.114 b;     blend(a, b, f) = clamp(f a + (1 - f) b, 0, 1)
+ *     brightness: blend(c, 0, f);   saturation: blend(c, gray(c), f)
+ *     contrast:   blend(c, m, f), m = the mean of gray over the item's points at that stage of the chain
+ *     hue:        RGB -> HSV (v = max, cr = max - min, s = cr / max or 0; rc, gc, bc = (max - r, g, b) / cr;
+ *                 h6 = bc - gc | 2 + rc - bc | 4 + gc - rc by the channel of the maximum; h = fmod(h6 / 6 + 1, 1)),
+ *                 h <- h + f wrapped into [0, 1), HSV -> RGB (i = floor(6h), t = 6h - i, p = clamp(v (1 - s)),
+ *                 q = clamp(v (1 - t s)), u = clamp(v (1 - (1 - t) s)), sectors (v,u,p) (q,v,p) (p,v,u) (p,q,v) (u,p,v) (v,p,q))
+ * The mean is a fixed-shape float64 sum over chunks of pcc_color_jitter_chunk() points counted from the
+ * item's first row (no float atomics): results are bitwise equal from run to run, and an item gives the
+ * same bytes alone and inside a batch.  Three launches whatever nbatch is.  scratch: 8-byte aligned,
+ * pcc_color_jitter_scratch_bytes(n, nbatch) bytes. */
+int32_t pcc_color_jitter_chunk(void);
+int64_t pcc_color_jitter_scratch_bytes(int64_t n, int32_t nbatch);
+int pcc_color_jitter(const float* rgb, int64_t n, const int64_t* offsets, int32_t nbatch, const float* params,
+                     const int32_t* order, float* out, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* Kernel map (ME kernel_map, cached per coordinate manager): for every output row j and
  * kernel offset k, nbr[j*K + k] = input row at c_out + sign * off_k * step, or -1.
  * sign = +1 for (strided) convolution with step = input tensor stride; sign = -1 for

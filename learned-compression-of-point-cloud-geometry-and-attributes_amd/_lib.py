@@ -27,6 +27,11 @@ SIGNATURES = {
     "pcc_scan_scratch_elems": (c_i64, [c_i64]),
     "pcc_stride_map": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pcc_children": (c_int, [c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pcc_augment_rotate": (c_int, [c_void_p, c_i64, c_void_p, c_i32, ctypes.c_float, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "pcc_color_jitter_chunk": (c_i32, []),
+    "pcc_color_jitter_scratch_bytes": (c_i64, [c_i64, c_i32]),
+    "pcc_color_jitter": (c_int, [c_void_p, c_i64, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "pcc_kernel_map": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pcc_pair_count": (c_int, [c_void_p, c_i64, c_void_p, c_void_p]),
     "pcc_conv_packed_elems": (c_i64, [c_i32, c_i32, c_i32]),
@@ -118,6 +123,7 @@ def build(force=False):
     check_kernel_resources()
     check_kernel_resources(os.path.join(_HERE, "build", "rans_lanes.resources.txt"), LANE_KERNELS)
     check_kernel_resources(os.path.join(_HERE, "build", "chconv.resources.txt"), CHCONV_KERNELS)
+    check_kernel_resources(os.path.join(_HERE, "build", "augment.resources.txt"), AUGMENT_KERNELS)
     check_small_kernel_lds_reads()
     return SO_PATH
 
@@ -132,6 +138,10 @@ LANE_KERNELS = ("rans_lanes_encode_kernel", "rans_lanes_pack_kernel", "rans_lane
 # the channelwise window convolution (csrc/chconv.hip): up to 1,331 probes and adds per output element run out of one
 # accumulator and a handful of probe registers, and a spill would sit inside that loop
 CHCONV_KERNELS = ("chconv_kernel",)
+# the training augmentation (csrc/augment.hip): the jitter's chain of four operations in a per-item order is unrolled over
+# registers, and an indexed (scratch) copy of it would sit in every point's path
+AUGMENT_KERNELS = ("jitter_partial_kernel", "jitter_mean_kernel", "jitter_apply_kernel", "rotate_clear_kernel", "rotate_insert_kernel",
+                   "rotate_flag_kernel", "rotate_finalize_kernel")
 
 
 def check_small_kernel_lds_reads(obj=None):

@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--ply", nargs="*", default=[])
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "weights.pt"))
     ap.add_argument("--log-every", type=int, default=20)
+    ap.add_argument("--augment", action="store_true",
+                    help="ColorJitter + RandomRotate on every batch, on the device (pcc_amd.augment.TrainAugment; configs/Ours.yaml:29-35)")
     args = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
@@ -76,10 +78,13 @@ def main():
             fs.append(torch.from_numpy(p[:, 3:6]))
         return sparse_collate(cs, fs)
 
+    augment = pcc_amd.augment.TrainAugment(block_size=args.block, seed=1234 + rank) if args.augment else None
     feed = pcc_amd.utils.Prefetcher(batch, depth=2)       # cut on a background thread, like the reference's DataLoader workers
     for step in range(1, args.steps + 1):
         C, F = next(feed)
         C, F = C.to(dev, non_blocking=True), F.to(dev, non_blocking=True)
+        if augment is not None:
+            C, F = augment(C, F)
         inp = pcc_amd.SparseTensor(coordinates=C, features=F, device=dev)
         Q, Lam = qgen(inp)
         opt.zero_grad(set_to_none=True)
@@ -93,11 +98,17 @@ def main():
         aux.backward()
         aux_red.finish()
         aux_opt.step()
+        if step == 1:
+            torch.cuda.synchronize()
+            t_first = time.time()
         if rank == 0 and (step % args.log_every == 0 or step == 1):
             print(f"step {step:5d}  loss {float(total.detach()):9.3f}  " +
                   "  ".join(f"{k} {float(v.detach()):.3f}" for k, v in parts.items()) +
                   f"  aux {float(aux.detach()):.1f}  {time.time() - t0:.0f} s", flush=True)
     feed.close()
+    torch.cuda.synchronize()
+    if rank == 0 and args.steps > 1:
+        print(f"mean step time {(time.time() - t_first) / (args.steps - 1) * 1e3:.1f} ms over steps 2..{args.steps}", flush=True)
     if rank == 0:
         model.eval()
         model.update()
