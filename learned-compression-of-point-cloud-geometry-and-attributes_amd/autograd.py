@@ -8,6 +8,9 @@ in model/, driven by train.py:194-206).  Here one ``torch.autograd.Function`` wr
               dW[k] = sum over pairs of X[i]^T dY[j]                      pcc_conv_wgrad
               db  = column sums of dY
 
+Maps, launches and packed weights are the inference path's (sparse.py: ``CoordMap.conv_map``, ``launch_conv``, the layer's cached
+``weights``); this module adds what autograd needs.
+
 The channelwise window convolution of the ColorSSIM loss (``ChannelwiseConvFn``) is its own node on pcc_chconv: forward
 with the window as given, backward-data the same kernel on dY with the window flipped.
 
@@ -20,9 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
-from .sparse import MODE_BF16, MODE_F32, MODE_X3, launch_mode, pack_weights
-
-_THIN_CIN = (1, 2, 3, 4, 6, 8, 12, 16, 24)
+from .sparse import ACT_LRELU, ACT_RELU, MODE_BF16, MODE_F32, _plan_takes, launch_conv, launch_mode, pack_weights
 
 # bf16 compute for the training path (BASELINE config 5: "bf16"): convolutions whose input width is a multiple of
 # 64 cast their input (forward: the features; backward-data: the output gradient) and weights to bf16 and run on
@@ -53,80 +54,22 @@ def _mode(rows, cin, cout, n_out, K, has_nbr):
     return launch_mode(BF16, X3, rows, cin, cout, n_out, K, has_nbr) if BF16 or X3 else MODE_F32
 
 
-def _launch_conv(feats, w, bias, nbr, order, gmask, n_out):
-    """feats: fp32, or an already cast bf16 copy (bf16 mode: one cast per tensor, shared by its consumers)"""
-    L = _lib.lib()
-    K, cin, cout = w.shape
-    rows = feats.shape[0]
-    mode = MODE_BF16 if feats.dtype == torch.bfloat16 else _mode(rows, cin, cout, n_out, K, nbr is not None)
-    out = torch.empty((n_out, cout), dtype=torch.float32, device=feats.device)
-    wp = pack_weights(w, mode)
-    if mode == MODE_BF16:
-        x = feats.to(torch.bfloat16)
-        check(L.pcc_conv_fwd_bf16(ptr(x), rows, cin, ptr(wp), ptr(bias), ptr(nbr), ptr(order), ptr(gmask), K, ptr(out), n_out, cout,
-                                  0, None, None, _lib.stream()))
-    elif mode == MODE_X3:
-        check(L.pcc_conv_fwd_x3(ptr(feats), rows, cin, ptr(wp), ptr(bias), ptr(nbr), ptr(order), ptr(gmask), K, ptr(out), n_out, cout,
-                                0, None, None, _lib.stream()))
-    else:
-        check(L.pcc_conv_fwd(ptr(feats), rows, cin, ptr(w), ptr(wp), ptr(bias), ptr(nbr), ptr(order), ptr(gmask), K, ptr(out), n_out,
-                             cout, 0, None, None, _lib.stream()))
-    return out
-
-
-def _forward_map(in_map, out_map, ksize, transposed, cin):
-    """(nbr, order, gmask) of the forward map; execution order when the MFMA kernels will run on it"""
-    if ksize == 1:
-        return None, None, None
-    if cin % 32 == 0:
-        nbr, order, gmask, _ = in_map.ordered_kernel_map(out_map, ksize, transposed)
-        return nbr, order, gmask
-    nbr, _, _ = in_map.kernel_map(out_map, ksize, transposed)
-    return nbr, None, None
-
-
-def _transposed_map(in_map, out_map, ksize, transposed):
-    """kernel map of the backward-data convolution: for input row i and offset k the output row that read i"""
-    from .sparse import ORDER_BLOCK_LOG2
-    key = ("tmap", id(out_map), ksize, transposed, ORDER_BLOCK_LOG2)
-    hit = in_map._cache.get(key)
-    if hit is not None and (hit[0] is out_map or (hit[0] is None and out_map is in_map)):
-        return hit[1:]
-    L = _lib.lib()
-    nbr, _, _ = in_map.kernel_map(out_map, ksize, transposed)
-    K = nbr.shape[1]
-    n_in, n_out = in_map.n, out_map.n
-    dev = nbr.device
-    nbr_t = torch.empty((n_in, K), dtype=torch.int32, device=dev)
-    mask_t = torch.empty(n_in, dtype=torch.int32, device=dev)
-    check(L.pcc_kernel_map_transpose(ptr(nbr), n_out, K, n_in, ptr(nbr_t), ptr(mask_t), _lib.stream()))
-    order = torch.empty(n_in, dtype=torch.int32, device=dev)
-    gmask = torch.empty((n_in + 31) // 32, dtype=torch.int32, device=dev)
-    nbytes = L.pcc_order_scratch_bytes(n_in)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    check(L.pcc_order_rows_by_mask(ptr(mask_t), ptr(in_map.coords), n_in, ORDER_BLOCK_LOG2, in_map.stride, ptr(order),
-                                   ptr(gmask), ptr(scratch), nbytes, _lib.stream()))
-    res = (nbr_t, order, gmask)
-    in_map._cache[key] = (None if out_map is in_map else out_map,) + res
-    return res
+def _taken_width(n_out, cout, cin, n_in, K, has_nbr):
+    """backward-data reads dY as its input: the first width >= cout that the fp32 plan takes (narrow dY is zero-padded to it)"""
+    return next((c for c in range(cout, cout + 32) if _plan_takes(MODE_F32, n_out, c, cin, n_in, K, has_nbr)), cout)
 
 
 class SparseConvFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feats, kernel, bias, in_map, out_map, ksize, transposed, out_channels):
+    def forward(ctx, feats, kernel, bias, layer, in_map, out_map, ksize, transposed, out_channels):
         feats = feats.contiguous()
-        w = kernel.detach()
-        if w.dim() == 2:
-            w = w.unsqueeze(0)
-        b = None if bias is None else bias.detach().reshape(-1)
-        if out_channels is not None:
-            w = w[:, :, :out_channels]
-            b = None if b is None else b[:out_channels].contiguous()
-        w = w.contiguous()
-        nbr, order, gmask = _forward_map(in_map, out_map, ksize, transposed, feats.shape[1])
-        if _mode(feats.shape[0], w.shape[1], w.shape[2], out_map.n, w.shape[0], nbr is not None) == MODE_BF16:
+        w, _, b = layer.weights(out_channels)
+        nbr, order, gmask, _ = in_map.conv_map(out_map, ksize, transposed, feats.shape[1])
+        mode = _mode(feats.shape[0], w.shape[1], w.shape[2], out_map.n, w.shape[0], nbr is not None)
+        if mode == MODE_BF16:
             feats = feats.to(torch.bfloat16)          # the one cast of this tensor: forward now, weight gradient later
-        out = _launch_conv(feats, w, b, nbr, order, gmask, out_map.n)
+        out = torch.empty((out_map.n, w.shape[2]), dtype=torch.float32, device=feats.device)
+        launch_conv(mode, feats, w, layer.packed(mode, out_channels), b, nbr, order, gmask, out)
         ctx.save_for_backward(feats, w)
         ctx.meta = (in_map, out_map, ksize, transposed, out_channels, tuple(kernel.shape), bias is not None)
         return out
@@ -200,22 +143,19 @@ class SparseConvFn(torch.autograd.Function):
 
         if ctx.needs_input_grad[0]:
             wt = w.transpose(1, 2)                                  # [K, cout, cin]
-            g = g_w if (ctx.needs_input_grad[1] and feats.dtype == torch.bfloat16 and cout % 64 == 0
-                        and _mode(n_out, cout, cin, n_in, K, ksize > 1) == MODE_BF16) else dy
-            if cout % 32 and cout not in _THIN_CIN:                 # input widths of the thin forward kernel: _THIN_CIN
-                pad = next(c for c in _THIN_CIN if c >= cout) - cout
-                g = torch.cat([dy, torch.zeros((n_out, pad), dtype=torch.float32, device=dev)], dim=1).contiguous()
-                wt = torch.cat([wt, torch.zeros((K, pad, cin), dtype=torch.float32, device=dev)], dim=1)
+            g = dy
+            width = _taken_width(n_out, cout, cin, n_in, K, ksize > 1)
+            if width != cout:
+                g = torch.cat([dy, torch.zeros((n_out, width - cout), dtype=torch.float32, device=dev)], dim=1).contiguous()
+                wt = torch.cat([wt, torch.zeros((K, width - cout, cin), dtype=torch.float32, device=dev)], dim=1)
             wt = wt.contiguous()
-            if ksize == 1:
-                d_feats = _launch_conv(g, wt, None, None, None, None, n_in)
-            else:
-                nbr_t, order_t, gmask_t = _transposed_map(in_map, out_map, ksize, transposed)
-                if g.shape[1] % 32 == 0:
-                    d_feats = _launch_conv(g, wt, None, nbr_t, order_t, gmask_t, n_in)
-                else:
-                    d_feats = _launch_conv(g, wt, None, nbr_t, None, None, n_in)
-        return d_feats, d_kernel, d_bias, None, None, None, None, None
+            mode = _mode(n_out, width, cin, n_in, K, ksize > 1)
+            if mode == MODE_BF16 and bf and ctx.needs_input_grad[1]:
+                g = g_w                                             # the bf16 copy the weight gradient made
+            nbr_t, order_t, gmask_t, _ = in_map.conv_map(out_map, ksize, transposed, width, adjoint=True)
+            d_feats = torch.empty((n_in, cin), dtype=torch.float32, device=dev)
+            launch_conv(mode, g, wt, pack_weights(wt, mode), None, nbr_t, order_t, gmask_t, d_feats)
+        return d_feats, d_kernel, d_bias, None, None, None, None, None, None
 
 
 class EpilogueFn(torch.autograd.Function):
@@ -254,16 +194,16 @@ def epilogue_train(c, film, residual, act):
         return EpilogueFn.apply(c, film, residual, act)
     if film is not None:
         c = c * film[:, :ch] + film[:, ch:]
-    if act == 1:
+    if act == ACT_RELU:
         c = torch.relu(c)
-    elif act == 2:
+    elif act == ACT_LRELU:
         c = torch.nn.functional.leaky_relu(c, 0.01)
     return c if residual is None else c + residual
 
 
 def conv_train(x_feats, in_map, out_map, layer, ksize, transposed, out_channels=None):
     """differentiable out = bias + conv(x) on the HIP kernels"""
-    return SparseConvFn.apply(x_feats, layer.kernel, layer.bias, in_map, out_map, ksize, transposed, out_channels)
+    return SparseConvFn.apply(x_feats, layer.kernel, layer.bias, layer, in_map, out_map, ksize, transposed, out_channels)
 
 
 def chconv_launch(feats, cmap, window, ksize, flip):

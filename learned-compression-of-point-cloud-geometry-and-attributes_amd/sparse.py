@@ -162,6 +162,20 @@ def _same_map(kept, out_map, self_map):
     return kept() is out_map
 
 
+def _order_buffers(n, dev):
+    """what an execution order of n rows is written into: (order int32 [n], group_mask32, scratch bytes)"""
+    return (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n + 31) // 32, dtype=torch.int32, device=dev),
+            torch.empty(_lib.lib().pcc_order_scratch_bytes(n), dtype=torch.uint8, device=dev))
+
+
+def _execution_order(row_mask, coords, n, stride):
+    """(order, group_mask32): the n rows sorted by neighbour mask, inside spatial blocks of ORDER_BLOCK_LOG2 voxels of `stride`"""
+    order, gmask, scratch = _order_buffers(n, coords.device)
+    check(_lib.lib().pcc_order_rows_by_mask(ptr(row_mask), ptr(coords), n, ORDER_BLOCK_LOG2, stride, ptr(order), ptr(gmask),
+                                            ptr(scratch), scratch.shape[0], _lib.stream()))
+    return order, gmask
+
+
 class CoordMap:
     """A coordinate set of one tensor stride with its hashed-voxel table and cached kernel maps.
 
@@ -258,12 +272,23 @@ class CoordMap:
             self._cache[key] = CoordMap(coords, self.stride // 2, table, self._nbatch)
         return self._cache[key]
 
+    def _cached_for(self, out_map, key):
+        """what _keep_for stored under `key` (which names id(out_map)) if that was for this `out_map`, else None"""
+        hit = self._cache.get(key)
+        return hit[1:] if hit is not None and _same_map(hit[0], out_map, self) else None
+
+    def _keep_for(self, out_map, key, *vals):
+        """cache `vals` under `key`; the entry remembers out_map weakly (_same_map): id() alone could be reused, a strong
+        reference makes cycles.  Returns vals."""
+        self._cache[key] = (None if out_map is self else weakref.ref(out_map),) + vals
+        return vals
+
     def kernel_map(self, out_map, ksize, transposed=False):
         """(nbr int32 [N_out, K], row_mask int32 [N_out], PairCount) for input=self, output=out_map."""
         key = ("kmap", id(out_map), ksize, transposed)
-        hit = self._cache.get(key)
-        if hit is not None and _same_map(hit[0], out_map, self):
-            return hit[1:]
+        hit = self._cached_for(out_map, key)
+        if hit is not None:
+            return hit
         keys, vals, cap = self.table()
         K = ksize ** 3
         n_out = out_map.n
@@ -278,9 +303,7 @@ class CoordMap:
         # hit, K indices and the mask written
         probes = K * n_out if not transposed else max(n_out, K * n_out // 8)
         _cp_end(ev, "kernel_map", n_out, lambda: 20 * n_out + 8 * probes + 4 * int(pairs) + 4 * K * n_out)
-        # the entry remembers out_map weakly (_same_map): id() alone could be reused, a strong reference makes cycles
-        self._cache[key] = (None if out_map is self else weakref.ref(out_map), nbr, row_mask, pairs)
-        return nbr, row_mask, pairs
+        return self._keep_for(out_map, key, nbr, row_mask, pairs)
 
     def ordered_kernel_map(self, out_map, ksize, transposed=False):
         """Kernel map with its MFMA execution order: (nbr [N_out, K] by output row, order [N_out], group_mask32, pair_count).
@@ -289,27 +312,19 @@ class CoordMap:
         MFMA tiles skip the offsets none of their rows has.  The table stays in output-row order — the kernels read row
         order[position] of it — so ordering a map writes 4 bytes per row, not a second copy of the table."""
         key = ("okmap", id(out_map), ksize, transposed, ORDER_BLOCK_LOG2)
-        hit = self._cache.get(key)
-        if hit is not None and _same_map(hit[0], out_map, self):
-            return hit[1:]
+        hit = self._cached_for(out_map, key)
+        if hit is not None:
+            return hit
         if (0 < out_map.n <= _small_map_max() and ksize in (2, 3) and ORDER_BLOCK_LOG2 < 0
                 and ("kmap", id(out_map), ksize, transposed) not in self._cache):
             return self._small_ordered_kernel_map(out_map, ksize, transposed, key)
         nbr, row_mask, pairs = self.kernel_map(out_map, ksize, transposed)
-        L = _lib.lib()
         n_out = nbr.shape[0]
-        dev = self.device
-        order = torch.empty(n_out, dtype=torch.int32, device=dev)
-        gmask = torch.empty((n_out + 31) // 32, dtype=torch.int32, device=dev)
-        nbytes = L.pcc_order_scratch_bytes(n_out)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         ev = _cp_begin()
-        check(L.pcc_order_rows_by_mask(ptr(row_mask), ptr(out_map.coords), n_out, ORDER_BLOCK_LOG2, out_map.stride,
-                                       ptr(order), ptr(gmask), ptr(scratch), nbytes, _lib.stream()))
+        order, gmask = _execution_order(row_mask, out_map.coords, n_out, out_map.stride)
         # offset counts 4 B, keys 4 + 4 B, four radix passes of (4 B counted + 8 B read + 8 B written), group masks 8 B per row
         _cp_end(ev, "execution_order", n_out, 100 * n_out)
-        self._cache[key] = (None if out_map is self else weakref.ref(out_map), nbr, order, gmask, pairs)
-        return nbr, order, gmask, pairs
+        return self._keep_for(out_map, key, nbr, order, gmask, pairs)
 
     def _small_ordered_kernel_map(self, out_map, ksize, transposed, key):
         """kernel_map + ordered_kernel_map of a small map in one launch (csrc/select.hip small_map_kernel); fills both caches"""
@@ -318,33 +333,55 @@ class CoordMap:
         n_out, K, dev = out_map.n, ksize ** 3, self.device
         nbr = torch.empty((n_out, K), dtype=torch.int32, device=dev)
         row_mask = torch.empty(n_out, dtype=torch.int32, device=dev)
-        order = torch.empty(n_out, dtype=torch.int32, device=dev)
-        gmask = torch.empty((n_out + 31) // 32, dtype=torch.int32, device=dev)
-        nbytes = L.pcc_order_scratch_bytes(n_out)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        order, gmask, scratch = _order_buffers(n_out, dev)
         step = self.stride // 2 if transposed else self.stride
         ev = _cp_begin()
         check(L.pcc_small_kernel_map(ptr(out_map.coords), n_out, ptr(keys), ptr(vals), cap, ksize, step, -1 if transposed else 1,
-                                     ptr(nbr), ptr(row_mask), ptr(order), ptr(gmask), ptr(scratch), nbytes, _lib.stream()))
+                                     ptr(nbr), ptr(row_mask), ptr(order), ptr(gmask), ptr(scratch), scratch.shape[0], _lib.stream()))
         pairs = PairCount(row_mask)
         _cp_end(ev, "small_map+order", n_out, (120 + 12 * K) * n_out)
-        keep = None if out_map is self else weakref.ref(out_map)
-        self._cache[("kmap", id(out_map), ksize, transposed)] = (keep, nbr, row_mask, pairs)
-        self._cache[key] = (keep, nbr, order, gmask, pairs)
-        return nbr, order, gmask, pairs
+        self._keep_for(out_map, ("kmap", id(out_map), ksize, transposed), nbr, row_mask, pairs)
+        return self._keep_for(out_map, key, nbr, order, gmask, pairs)
 
     def position_ordered_table(self, out_map, ksize, transposed=False):
         """the kernel map's table permuted into execution order (nbr[order]) for the weight-gradient kernels of the training
         path, which index it by execution position (csrc/conv_bwd.hip): (nbr_sorted, order, group_mask32, pair_count)"""
         key = ("okmap_sorted", id(out_map), ksize, transposed, ORDER_BLOCK_LOG2)
-        hit = self._cache.get(key)
-        if hit is not None and _same_map(hit[0], out_map, self):
-            return hit[1:]
+        hit = self._cached_for(out_map, key)
+        if hit is not None:
+            return hit
         nbr, order, gmask, pairs = self.ordered_kernel_map(out_map, ksize, transposed)
         nbr_sorted = torch.empty_like(nbr)
         check(_lib.lib().pcc_permute_map_rows(ptr(nbr), ptr(order), nbr.shape[0], nbr.shape[1], ptr(nbr_sorted), _lib.stream()))
-        self._cache[key] = (None if out_map is self else weakref.ref(out_map), nbr_sorted, order, gmask, pairs)
-        return nbr_sorted, order, gmask, pairs
+        return self._keep_for(out_map, key, nbr_sorted, order, gmask, pairs)
+
+    def transposed_ordered_map(self, out_map, ksize, transposed=False):
+        """Kernel map of the backward-data convolution with its execution order: (nbr_t int32 [N_in, K] — for input row i and
+        offset k the output row that read i —, order [N_in], group_mask32)"""
+        key = ("tmap", id(out_map), ksize, transposed, ORDER_BLOCK_LOG2)
+        hit = self._cached_for(out_map, key)
+        if hit is not None:
+            return hit
+        nbr, _, _ = self.kernel_map(out_map, ksize, transposed)
+        n_out, K = nbr.shape
+        nbr_t = torch.empty((self.n, K), dtype=torch.int32, device=self.device)
+        mask_t = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        check(_lib.lib().pcc_kernel_map_transpose(ptr(nbr), n_out, K, self.n, ptr(nbr_t), ptr(mask_t), _lib.stream()))
+        return self._keep_for(out_map, key, nbr_t, *_execution_order(mask_t, self.coords, self.n, self.stride))
+
+    def conv_map(self, out_map, ksize, transposed, cin, adjoint=False):
+        """The map form a convolution of input width `cin` runs on, (nbr, order, group_mask32, pair_count): none for kernel
+        size 1, the execution-ordered map where the MFMA kernels run (cin % 32 == 0), else the plain map.  adjoint: the
+        backward-data convolution of the same layer (cin = the width of its dY), on the transposed map, pairs not counted."""
+        if ksize == 1:
+            return None, None, None, None
+        if adjoint:
+            nbr, order, gmask = self.transposed_ordered_map(out_map, ksize, transposed)
+            return (nbr, order, gmask, None) if cin % 32 == 0 else (nbr, None, None, None)
+        if cin % 32 == 0:
+            return self.ordered_kernel_map(out_map, ksize, transposed)
+        nbr, _, pairs = self.kernel_map(out_map, ksize, transposed)
+        return nbr, None, None, pairs
 
     def mfma_kernel_map(self, out_map, ksize, transposed=False):
         """Build (and cache) the map form the wide inference convolutions will ask for — what the prefetchers call"""
@@ -588,19 +625,11 @@ def conv_forward(x_feats, in_map, out_map, layer, ksize, transposed=False, act=A
     cout = w.shape[-1]
     if ksize > 1 and cin % 32 == 0 and cout <= NARROW_HEAD_MAX_COUT and film is None and residual is None:
         return _narrow_head_forward(x_feats, in_map, out_map, layer, ksize, transposed, act, out_channels)
-    order = gmask = None
     if (ksize > 1 and cin in (1, 2, 4, 8) and cout % 32 == 0 and ksize ** 3 * cin <= 256
             and out_map.n * ((ksize ** 3 * cin + 31) // 32 * 32) * 4 < 0xFFFFF000):
         return _thin_im2col_forward(x_feats, in_map, out_map, layer, ksize, transposed, act, film, residual, out_channels)
-    if ksize == 1:
-        nbr = pairs = None
-        K = 1
-    elif cin % 32 == 0:
-        nbr, order, gmask, pairs = in_map.ordered_kernel_map(out_map, ksize, transposed)
-        K = ksize ** 3
-    else:
-        nbr, _, pairs = in_map.kernel_map(out_map, ksize, transposed)
-        K = ksize ** 3
+    nbr, order, gmask, pairs = in_map.conv_map(out_map, ksize, transposed, cin)
+    K = ksize ** 3
     n_out = out_map.n
     out = torch.empty((n_out, cout), dtype=torch.float32, device=x_feats.device)
     mode = launch_mode(INFER_BF16, INFER_X3, n_in, cin, cout, n_out, K, nbr is not None) if INFER_BF16 or INFER_X3 else MODE_F32
@@ -618,16 +647,7 @@ def conv_forward(x_feats, in_map, out_map, layer, ksize, transposed=False, act=A
                          None, None, gmask))
         return out
     ev0 = _prof_begin(timed)
-    if mode == MODE_BF16:
-        xb = x_feats.to(torch.bfloat16)
-        check(L.pcc_conv_fwd_bf16(ptr(xb), n_in, cin, ptr(layer.weights_bf16(out_channels)), ptr(bias), ptr(nbr),
-                                  ptr(order), ptr(gmask), K, ptr(out), n_out, cout, act, ptr(film), ptr(residual), _lib.stream()))
-    elif mode == MODE_X3:
-        check(L.pcc_conv_fwd_x3(ptr(x_feats), n_in, cin, ptr(layer.weights_x3(out_channels)), ptr(bias), ptr(nbr),
-                                ptr(order), ptr(gmask), K, ptr(out), n_out, cout, act, ptr(film), ptr(residual), _lib.stream()))
-    else:
-        check(L.pcc_conv_fwd(ptr(x_feats), n_in, cin, ptr(w), ptr(wp), ptr(bias), ptr(nbr), ptr(order), ptr(gmask),
-                             K, ptr(out), n_out, cout, act, ptr(film), ptr(residual), _lib.stream()))
+    launch_conv(mode, x_feats, w, layer.packed(mode, out_channels), bias, nbr, order, gmask, out, act, film, residual)
     # the launch's name is worked out by the reader (profiled_name): string building has no place between two launches
     _prof_end(ev0, ("conv", mode, n_in, K, nbr is not None), cin, cout, pairs if pairs is not None else n_out, n_out, gmask)
     return out
@@ -787,6 +807,24 @@ def _plan_takes(mode, n_in, cin, cout, n_out, K, has_nbr):
     return _lib.lib().pcc_conv_kernel_name(mode, n_in, cin, cout, n_out, K, int(has_nbr), None, 0) == 0
 
 
+def launch_conv(mode, feats, w, wp, bias, nbr, order, gmask, out, act=ACT_NONE, film=None, residual=None):
+    """One convolution launch in the arithmetic of ``mode`` into ``out`` [n_out, cout].  feats: fp32 — cast here for MODE_BF16 —
+    or an already cast bf16 tensor, taken as it is (the training path casts a tensor once for all its consumers);
+    w: the [K, cin, cout] kernel (read by the fp32 kernels of thin inputs); wp: its packing for ``mode`` (pack_weights)."""
+    L = _lib.lib()
+    K, cin, cout = w.shape
+    n_in, n_out = feats.shape[0], out.shape[0]
+    if mode == MODE_BF16:
+        check(L.pcc_conv_fwd_bf16(ptr(feats.to(torch.bfloat16)), n_in, cin, ptr(wp), ptr(bias), ptr(nbr), ptr(order), ptr(gmask), K,
+                                  ptr(out), n_out, cout, act, ptr(film), ptr(residual), _lib.stream()))
+    elif mode == MODE_X3:
+        check(L.pcc_conv_fwd_x3(ptr(feats), n_in, cin, ptr(wp), ptr(bias), ptr(nbr), ptr(order), ptr(gmask), K, ptr(out), n_out,
+                                cout, act, ptr(film), ptr(residual), _lib.stream()))
+    else:
+        check(L.pcc_conv_fwd(ptr(feats), n_in, cin, ptr(w), ptr(wp), ptr(bias), ptr(nbr), ptr(order), ptr(gmask), K, ptr(out),
+                             n_out, cout, act, ptr(film), ptr(residual), _lib.stream()))
+
+
 def pack_weights(w, mode=MODE_F32):
     """[K, cin, cout] fp32 kernel -> the layout the convolution kernel of ``mode`` reads (fp32 MFMA packing, bf16 packing,
     three bf16 planes); None for fp32 thin inputs (cin % 32 != 0), whose kernel reads ``w`` itself."""
@@ -874,6 +912,12 @@ class _ConvBase(nn.Module):
     def weights_x3(self, out_channels=None):
         """three-plane bf16 packing of the kernel (opt-in split-bf16 arithmetic)"""
         return pack_weights(self.weights(out_channels)[0], MODE_X3)
+
+    def packed(self, mode, out_channels=None):
+        """the kernel in the layout a launch of ``mode`` reads (launch_conv's ``wp``)"""
+        if mode == MODE_BF16:
+            return self.weights_bf16(out_channels)
+        return self.weights_x3(out_channels) if mode == MODE_X3 else self.weights(out_channels)[1]
 
     @_cached_weights("i")
     def im2col_weights(self, out_channels=None):

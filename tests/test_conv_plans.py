@@ -111,6 +111,30 @@ def test_table_reaches_every_kernel_the_planner_can_emit(pcc):
     assert len(twins) == 2 * len(cp.FP32_TILES) and not twins - {c.kernel for c in GLOBAL_CASES}, sorted(twins - {c.kernel for c in GLOBAL_CASES})
 
 
+@pytest.mark.parametrize("K", [1, 8, 27])
+def test_backward_data_pads_dy_to_the_widths_the_thin_plan_takes(pcc, K):
+    """The training path's backward-data convolution reads dY [n_out, cout] as its input and zero-pads a narrow one to the
+    first width the fp32 plan takes (autograd._taken_width asks the planner).  That used to be a hand copy of thin_cin()
+    (csrc/conv.hip), the tuple below: wherever the plan takes the tuple's width — every shape that ran — the planner's answer
+    is that width; where it does not (no width of the tuple fits, or the thin kernel's weights would pass its 160 KB of LDS:
+    the launch was an error), it is the next multiple of 32, the MFMA kernel."""
+    from pcc_amd import autograd, sparse as sp
+    old_tuple = (1, 2, 3, 4, 6, 8, 12, 16, 24)
+    cin, n = 64, 9500
+    ran = []
+    for cout in range(1, 32):
+        old = next((c for c in old_tuple if c >= cout), None)
+        got = autograd._taken_width(n, cout, cin, n, K, K > 1)
+        if old is not None and sp._plan_takes(sp.MODE_F32, n, old, cin, n, K, K > 1):
+            ran.append(cout)
+            assert got == old, (cout, got, old)
+        else:
+            assert got == 32, (cout, got)
+    # 27 x 24 x 64 floats are 162 KB: with 27 offsets the widest thin width that ran is 16
+    assert ran == list(range(1, 17 if K == 27 else 25))
+    assert [autograd._taken_width(n, c, cin, n, K, K > 1) for c in (32, 64, 128, 256)] == [32, 64, 128, 256]
+
+
 @pytest.mark.parametrize("n_out,n_in,K", [(50003, 25008, 27), (6001, 1, 27), (96007, 97008, 27), (33, 36, 3), (1, 5, 27)])
 def test_synthetic_map_has_the_planted_corners(n_out, n_in, K):
     m = cp.build_map(n_out, n_in, K)

@@ -260,3 +260,67 @@ def test_cast_and_column_sums_in_one_pass(pcc, n, ch):
         xn[0, 0] = float("nan")
         check(L.pcc_cast_colsum(ptr(xn), n, ch, ptr(out), None, None, 0, _lib.stream()))
         assert torch.equal(out.view(torch.int16), xn.to(torch.bfloat16).view(torch.int16))
+
+
+@pytest.mark.parametrize("onto", ["ancestor", "same"])
+def test_training_maps_are_freed_by_reference_count(pcc, onto):
+    """A training step's maps go back to the allocator when the step drops them, without the cyclic collector: no cache entry
+    of a CoordMap holds another map strongly except "down" / ("up", k), which point away from the ancestor.  `ancestor`: a
+    generative transposed layer evaluated on m.down() at the given coordinates of m itself, so the forward, transposed and
+    position-ordered maps cached on the child all name the parent (kept strongly, parent -> "down" -> child -> entry -> parent
+    is a cycle); `same`: a stride-1 layer (out_map is in_map: the entries remember no map at all)."""
+    import gc
+    import weakref
+    torch.manual_seed(13)
+    gc.collect()
+    gc.disable()
+    try:
+        m = pcc.CoordMap(torch.from_numpy(shell()).to(DEV), 1)
+        d = m.down()
+        if onto == "ancestor":
+            layer = pcc.MinkowskiGenerativeConvolutionTranspose(64, 64, kernel_size=3, stride=2, bias=True, dimension=3).to(DEV)
+            in_map = d
+        else:
+            layer = pcc.MinkowskiConvolution(64, 64, kernel_size=3, stride=1, bias=True, dimension=3).to(DEV)
+            in_map = m
+        x = torch.randn(in_map.n, 64, device=DEV).requires_grad_(True)
+        out = layer(pcc.SparseTensor(x, coordinate_map=in_map), out_map=m)
+        assert out.map is m and out.F.shape == (m.n, 64)
+        out.F.square().sum().backward()
+        assert x.grad is not None and layer.kernel.grad is not None
+        assert any(k[0] == "tmap" for k in in_map._cache if isinstance(k, tuple))          # the backward-data map was cached
+        alive_m, alive_d = weakref.ref(m), weakref.ref(d)
+        del m, d, in_map, x, out, layer
+        assert alive_m() is None and alive_d() is None
+    finally:
+        gc.enable()
+
+
+@pytest.mark.parametrize("kind", ["down", "up3"])
+def test_transposed_ordered_map_equals_the_direct_calls(pcc, kind):
+    """CoordMap.transposed_ordered_map = pcc_kernel_map_transpose of the kernel map + pcc_order_rows_by_mask over the INPUT
+    set's coordinates and stride, bit for bit, and cached"""
+    from pcc_amd import _lib, sparse as sp
+    from pcc_amd._lib import check, ptr
+    L = pcc.lib()
+    m = pcc.CoordMap(torch.from_numpy(shell() * np.array([1, 2, 2, 2], dtype=np.int32)).to(DEV), 2)
+    out_map, tr = (m.down(), False) if kind == "down" else (m.up(3), True)
+    got = m.transposed_ordered_map(out_map, 3, tr)
+    nbr, _, _ = m.kernel_map(out_map, 3, tr)
+    n_in, n_out, K = m.n, out_map.n, 27
+    assert nbr.shape == (n_out, K)
+    nbr_t = torch.full((n_in, K), -7, dtype=torch.int32, device=DEV)
+    mask_t = torch.full((n_in,), -7, dtype=torch.int32, device=DEV)
+    check(L.pcc_kernel_map_transpose(ptr(nbr), n_out, K, n_in, ptr(nbr_t), ptr(mask_t), _lib.stream()))
+    order = torch.full((n_in,), -7, dtype=torch.int32, device=DEV)
+    gmask = torch.full(((n_in + 31) // 32,), -7, dtype=torch.int32, device=DEV)
+    nbytes = L.pcc_order_scratch_bytes(n_in)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    check(L.pcc_order_rows_by_mask(ptr(mask_t), ptr(m.coords), n_in, sp.ORDER_BLOCK_LOG2, m.stride, ptr(order), ptr(gmask),
+                                   ptr(scratch), nbytes, _lib.stream()))
+    assert len(got) == 3
+    for name, a, b in zip(("nbr_t", "order", "gmask"), got, (nbr_t, order, gmask)):
+        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), name
+    assert torch.equal(torch.sort(got[1].long()).values, torch.arange(n_in, device=DEV))       # a permutation of the input rows
+    again = m.transposed_ordered_map(out_map, 3, tr)
+    assert all(a is b for a, b in zip(again, got))
