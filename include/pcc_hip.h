@@ -434,6 +434,23 @@ int pcc_nn_search(const int32_t* query, int64_t nq, const uint64_t* keys, const 
                   int32_t* tie_count, double* tie_rgb, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Surface normals of a voxelised cloud (point-to-plane / D2 PSNR, facing quality maps).  Replaces
+ * open3d's estimate_normals (evaluate_view_dep.py:354-376).  coords [n,4] = (batch, x, y, z);
+ * keys / vals / cap / tensor_stride: the hash table of the SAME cloud (pcc_hash_build).  The
+ * neighbourhood of a point p is every occupied voxel q of its batch item with d = q - p and
+ * d.d <= radius^2 (p included; radius 1..8).  count [n] (optional) = its size; moments [n,6]
+ * (optional) = the upper triangle (xx, xy, xz, yy, yz, zz) of M = count * sum(d d^T) -
+ * sum(d) sum(d)^T, exact integers.  normals [n,3] (f64) = the unit eigenvector of M's smallest
+ * eigenvalue (cyclic Jacobi, fixed order and sweeps: bitwise reproducible), or (0,0,0) where
+ * count < 3 or the neighbours are collinear (sum of M's principal 2 x 2 minors <= 0, in int64).
+ * orient_mode 0: sign as computed; 1: n.orient >= 0; 2: n.(orient - p) >= 0 (orient = a camera
+ * position).  orient: 3 HOST doubles (may be NULL in mode 0).
+ * ------------------------------------------------------------------------------------- */
+int pcc_estimate_normals(const int32_t* coords, int64_t n, const uint64_t* keys, const int32_t* vals, int64_t cap,
+                         int32_t tensor_stride, int32_t radius, int32_t orient_mode, const double* orient,
+                         double* normals, int32_t* count, int64_t* moments, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * View rendering and view metrics of the view-dependent / region-of-interest evaluation
  * (evaluate_view_dep.py:102-305).
  *

@@ -20,6 +20,7 @@ from .blocks import ScaledBlock, GenerativeUpBlock, ConditionEncoder  # noqa: F4
 from .transforms import AnalysisTransform, SparseSynthesisTransform  # noqa: F401
 from .entropy_models import MeanScaleHyperprior, MeanScaleHyperprior_Map  # noqa: F401
 from .model import ColorModel  # noqa: F401
+from .normals import estimate_normals  # noqa: F401
 from . import synthetic, utils, parallel, render, augment  # noqa: F401
 
-__all__ = ["ColorModel", "SparseTensor", "CoordMap", "build", "lib"]
+__all__ = ["ColorModel", "SparseTensor", "CoordMap", "build", "lib", "estimate_normals"]

@@ -89,6 +89,8 @@ SIGNATURES = {
     "pcc_octree_expand": (c_int, [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),
     "pcc_nn_search": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
+    "pcc_estimate_normals": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
     "pcc_eb_quantize": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pcc_eb_dequantize": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p]),
     "pcc_eb_likelihood": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p]),
@@ -124,6 +126,7 @@ def build(force=False):
     check_kernel_resources(os.path.join(_HERE, "build", "rans_lanes.resources.txt"), LANE_KERNELS)
     check_kernel_resources(os.path.join(_HERE, "build", "chconv.resources.txt"), CHCONV_KERNELS)
     check_kernel_resources(os.path.join(_HERE, "build", "augment.resources.txt"), AUGMENT_KERNELS)
+    check_kernel_resources(os.path.join(_HERE, "build", "normals.resources.txt"), NORMALS_KERNELS)
     check_small_kernel_lds_reads()
     return SO_PATH
 
@@ -142,6 +145,10 @@ CHCONV_KERNELS = ("chconv_kernel",)
 # registers, and an indexed (scratch) copy of it would sit in every point's path
 AUGMENT_KERNELS = ("jitter_partial_kernel", "jitter_mean_kernel", "jitter_apply_kernel", "rotate_clear_kernel", "rotate_insert_kernel",
                    "rotate_flag_kernel", "rotate_finalize_kernel")
+
+# the surface normals (csrc/normals.hip): the 3 x 3 Jacobi iteration runs over named scalars, and an indexed (scratch) copy of the
+# matrix would put a memory round trip into every one of its 36 rotations
+NORMALS_KERNELS = ("estimate_normals_kernel",)
 
 
 def check_small_kernel_lds_reads(obj=None):

@@ -19,6 +19,8 @@ import torch
 from . import render
 from .io import write_png
 from .metrics import PointCloudMetric
+from .normals import estimate_normals
+from .q_map import facing_score
 from .sparse import SparseTensor
 
 
@@ -61,14 +63,19 @@ def compress_model_ours(experiment, model, data, q_a, q_g, device, base_path):
     return source, reconstruction, bpp, t_compress, t_decompress
 
 
-def evaluate_frame(experiment, model, data, q_a, q_g, device, base_path, resolution=1023):
-    """one row of the sweep table (evaluate.py:100-160): rate, times, D1 and colour PSNRs"""
+def evaluate_frame(experiment, model, data, q_a, q_g, device, base_path, resolution=1023, d2_radius=None):
+    """one row of the sweep table (evaluate.py:100-160): rate, times, D1 and colour PSNRs; with ``d2_radius`` (the radius of the
+    normal estimation, in voxels) also ``sym_d2_psnr``, the point-to-plane figure of utils.py:263-288"""
     src, rec, bpp, t_c, t_d = compress_model_ours(experiment, model, data, q_a, q_g, device, base_path)
-    res, _ = PointCloudMetric(src, rec, resolution=resolution, device=device).compute_pointcloud_metrics(drop_duplicates=True)
-    return {"q_g": float(np.mean(q_g)), "q_a": float(np.mean(q_a)), "bpp": bpp, "t_compress": t_c, "t_decompress": t_d,
+    metric = PointCloudMetric(src, rec, resolution=resolution, device=device)
+    res, _ = metric.compute_pointcloud_metrics(drop_duplicates=True)
+    row = {"q_g": float(np.mean(q_g)), "q_a": float(np.mean(q_a)), "bpp": bpp, "t_compress": t_c, "t_decompress": t_d,
             "n_source": int(src.shape[0]), "n_decoded": int(rec.shape[0]),
             "sym_p2p_psnr": res["sym_psnr_mse"], "sym_y_psnr": res["sym_y_psnr"], "sym_u_psnr": res["sym_u_psnr"],
             "sym_v_psnr": res["sym_v_psnr"]}
+    if d2_radius is not None:
+        row["sym_d2_psnr"] = metric.compute_d2(radius=d2_radius)["sym_d2_psnr"]
+    return row
 
 
 def _extent(points, axis):
@@ -77,9 +84,13 @@ def _extent(points, axis):
 
 
 def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path, view="front", H=1024, W=512, gradient=None, roi=None,
-                            save_images=False, details=None):
+                            save_images=False, details=None, facing=None):
     """The three rows of evaluate_view_dep.py:139-301 for one frame -> {"uniform": row, "view": row, "roi": row}, each row
     {"bpp", "q_a", "q_g", "key", "psnr", "ssim"}.
+
+    ``facing`` (a dict) appends a fourth row "facing", judged by the same rendered view: quality by the angle between each
+    point's normal and the viewing ray (q_map.facing_score; evaluate_view_dep.py:354-376).  Its keys: ``radius`` of the normal
+    estimation (3), ``camera`` (a position) or ``direction`` (the view's front axis when neither is given), ``floor`` (0.0).
 
     ``view``: a preset of render.VIEWS or a (front, up) pair.  ``gradient=(axis, lo, hi)``: the view-dependent map, score =
     clip((p[axis] - lo) / (hi - lo), 0, 1) with axis 0..2 over x, y, z (:209-215; lo > hi makes quality rise towards
@@ -90,7 +101,7 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
 
     All four images (the source and the three reconstructions) are rendered in the SOURCE's frame.  ``save_images`` writes
     them as PNG under ``<base_path>/<experiment>/renders_view/`` (the reference's names, :188-278).  ``details`` (a dict)
-    receives ``{"source" | "uniform" | "view" | "roi": (cloud, image)}`` for callers that want the tensors."""
+    receives ``{"source" | "uniform" | "view" | "roi" (| "facing"): (cloud, image)}`` for callers that want the tensors."""
     front, up = render._view(view)
     right, up, front = render.view_axes(front, up)
     tag = view if isinstance(view, str) else "custom"
@@ -110,6 +121,12 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
         "view": torch.clamp((points[:, g_axis] - float(g_lo)) / (float(g_hi) - float(g_lo)), 0, 1),
         "roi": (points[:, r_axis] >= float(r_plane)).to(torch.float),
     }
+    if facing is not None:
+        camera, direction = facing.get("camera"), facing.get("direction")
+        if camera is None and direction is None:
+            direction = front
+        normals, _ = estimate_normals(points, radius=facing.get("radius", 3))
+        maps["facing"] = facing_score(points, normals, camera, direction, facing.get("floor", 0.0)).to(torch.float)
     img_dir = os.path.join(base_path, experiment, "renders_view")
     if save_images:
         os.makedirs(img_dir, exist_ok=True)

@@ -1,4 +1,4 @@
-"""Quality metrics on the GPU: D1 (point-to-point) PSNR, Y/U/V PSNR, and Bjontegaard deltas.
+"""Quality metrics on the GPU: D1 (point-to-point) and D2 (point-to-plane) PSNR, Y/U/V PSNR, and Bjontegaard deltas.
 
 ``PointCloudMetric`` mirrors /root/reference/metrics/metric.py:6-189 (same result keys, same
 formulas, same two modes of ``compute_pointcloud_metrics``); the open3d KD-tree association
@@ -6,6 +6,9 @@ formulas, same two modes of ``compute_pointcloud_metrics``); the open3d KD-tree 
 as ``[N, 6]`` tensors on the GPU (xyz voxel indices, rgb in [0, 1]) instead of open3d objects or
 PLY paths.  Equidistant neighbours — the rule on a lattice, and resolved by KD-tree visiting order
 in the reference — resolve to the smallest (x, y, z) here.
+
+``compute_d2`` adds the point-to-plane figures the reference's sweep table parses from the MPEG metric tool
+(utils.py:263-288: ``sym_d2_mse`` / ``sym_d2_psnr``), on normals estimated from the source (normals.py).
 
 ``Bjontegaard_Model`` / ``Bjontegaard_Delta`` mirror metrics/bjontegaard.py:6-79 (cubic fits in the
 log10-rate domain; host-side numpy, a handful of points per curve).
@@ -17,6 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
+from .normals import estimate_normals
 from .sparse import CoordMap
 
 _RADII = (2, 8, 32, 128, 1024)      # widening schedule of the shell search
@@ -149,6 +153,33 @@ class PointCloudMetric:
         for name in ("mse", "hausdorff", "psnr_mse", "psnr_hausdorff", "y_mse", "u_mse", "v_mse", "y_psnr", "u_psnr", "v_psnr"):
             result["sym_" + name] = min(result["AB_" + name], result["BA_" + name])
         return result, error_vectors
+
+    def compute_d2(self, radius=3):
+        """Point-to-plane (D2) error beside D1, on the associations the constructor holds.  Normals n_A are estimated on the
+        source (``radius`` voxels); a reconstructed point carries the normal of its own nearest source point, as the MPEG
+        tool carries the original's normals onto the decoded cloud.  A -> B: ((a - b) . n_B(b))^2 for a's nearest b; B -> A:
+        ((b - a) . n_A(a))^2 for b's nearest a.  Where the normal used is invalid (zero) the point contributes its full
+        squared distance, so D2 <= D1 term by term.  ``*_d2_mse`` = mean error / 3 and ``*_d2_psnr`` = 10 log10(resolution^2 /
+        mse) follow the class's D1 keys (= 10 log10(3 peak^2 / mean error), the MPEG convention); ``sym_d2_*`` take the worse
+        direction, as the MPEG tool does (the class's older ``sym_*`` keys keep the reference's ``min``)."""
+        n_a, _ = estimate_normals(self.source_points, radius=radius, coord_map=self.source_map)
+        a, b = self.source_points[:, 1:4].to(torch.float64), self.recons_points[:, 1:4].to(torch.float64)
+        ab, ab_d2 = self.source_2_recons[0].long(), self.source_2_recons[1].to(torch.float64)
+        ba, ba_d2 = self.recons_2_source[0].long(), self.recons_2_source[1].to(torch.float64)
+        n_b = n_a.index_select(0, ba)
+        peak = float(self.resolution) ** 2
+        result = {}
+        for prefix, diff, normal, d2 in (("AB_", a - b.index_select(0, ab), n_b.index_select(0, ab), ab_d2),
+                                         ("BA_", b - a.index_select(0, ba), n_a.index_select(0, ba), ba_d2)):
+            proj = torch.minimum((diff * normal).sum(dim=1) ** 2, d2)      # |n| = 1 up to rounding: never above the distance
+            err = torch.where((normal != 0).any(dim=1), proj, d2)
+            err = err / _scalar(3.0, err)
+            mse = float(err.mean())
+            result[prefix + "d2_mse"] = mse
+            result[prefix + "d2_psnr"] = _psnr(peak, mse)
+        result["sym_d2_mse"] = max(result["AB_d2_mse"], result["BA_d2_mse"])
+        result["sym_d2_psnr"] = min(result["AB_d2_psnr"], result["BA_d2_psnr"])
+        return result
 
     def compute_metrics(self, mirror=False, drop_duplicates=False):
         if not mirror:

@@ -6,7 +6,9 @@ batch item, either a linear gradient along a random axis or a uniform map with r
 reference's training-time generator, driven by Python's ``random`` like the reference so that a
 seeded run draws the same maps — and returns it together with the lambda map used by the losses.
 ``uniform_map`` / ``gradient_map`` / ``view_dependent_map`` / ``roi_map`` build the fixed maps of the
-evaluation scripts (utils.py:436-445, evaluate_view_dep.py:207-260).  Elementwise work on [N, 2] tensors; plain torch.
+evaluation scripts (utils.py:436-445, evaluate_view_dep.py:207-260); ``facing_map`` is the second half of the view-dependent
+experiment (evaluate_view_dep.py:354-376): quality by the angle between a point's normal and the viewing ray.  Elementwise work
+on [N, 2] tensors; plain torch.
 """
 import math
 import random
@@ -44,6 +46,27 @@ def roi_map(coords_map, q_g, q_a, axis, plane):
     """evaluate_view_dep.py:254-260: region of interest — full quality where p[axis] >= plane, zero below"""
     score = (coords_map.coords[:, axis] >= plane).to(torch.float32)
     return SparseTensor(torch.stack([float(q_g) * score, float(q_a) * score], dim=1).contiguous(), coordinate_map=coords_map)
+
+
+def facing_score(points, normals, camera=None, direction=None, floor=0.0):
+    """float64 [N]: floor + (1 - floor) * |n . v| with v the unit vector from the point to ``camera`` or the fixed unit
+    ``direction``; a point without a normal (zero) scores 1"""
+    if (camera is None) == (direction is None):
+        raise ValueError("facing map: give a camera position or a direction (one of them)")
+    p, n = points.to(torch.float64), normals.to(torch.float64)
+    v = torch.as_tensor(camera if camera is not None else direction, dtype=torch.float64, device=p.device).reshape(1, 3)
+    if camera is not None:
+        v = v - p
+    v = v / torch.linalg.vector_norm(v, dim=1, keepdim=True).clamp_min(1e-300)
+    score = float(floor) + (1.0 - float(floor)) * (n * v).sum(dim=1).abs()
+    return torch.where((n != 0).any(dim=1), score, torch.ones_like(score))
+
+
+def facing_map(coords_map, normals, q_g, q_a, camera=None, direction=None, floor=0.0):
+    """quality by how squarely a surface faces the viewer: score = floor + (1 - floor) * |n . v| (facing_score), channels
+    [q_g * score, q_a * score]; ``normals``: float64 [N, 3] of normals.estimate_normals on the map's coordinates"""
+    score = facing_score(coords_map.coords[:, 1:4], normals, camera, direction, floor)
+    return SparseTensor(torch.stack([float(q_g) * score, float(q_a) * score], dim=1).to(torch.float32).contiguous(), coordinate_map=coords_map)
 
 
 class Q_Map:

@@ -9,7 +9,9 @@ The frame is a PLY path or a synthetic shell ("config1", "config2", or --grid / 
 numbers the reference keeps per sequence (:58-77) are arguments here; left out, they follow the frame's extent.
 
 usage: view_dep.py [config1 | config2 | frame.ply] [--out DIR] [--view front|side] [--height 1024] [--width 512]
-                   [--q-g 0.4] [--q-a 0.8] [--gradient AXIS LO HI] [--roi AXIS PLANE] [--weights W.pt] [--repeat N]"""
+                   [--q-g 0.4] [--q-a 0.8] [--gradient AXIS LO HI] [--roi AXIS PLANE] [--weights W.pt] [--repeat N]
+                   [--facing [--facing-radius 3] [--facing-floor 0.0]]     (a fourth row: quality by the angle between the
+                   points' normals and the viewing direction)"""
 import argparse
 import csv
 import json
@@ -41,6 +43,9 @@ def main():
     ap.add_argument("--grid", type=int)
     ap.add_argument("--radius", type=float)
     ap.add_argument("--weights")
+    ap.add_argument("--facing", action="store_true", help="add the facing row: quality by the normals' angle to the view's front axis")
+    ap.add_argument("--facing-radius", type=int, default=3)
+    ap.add_argument("--facing-floor", type=float, default=0.0)
     ap.add_argument("--repeat", type=int, default=0, help="time render_view and view_metrics over N further calls")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
@@ -61,9 +66,10 @@ def main():
     gradient = None if a.gradient is None else (int(a.gradient[0]), a.gradient[1], a.gradient[2])
     roi = None if a.roi is None else (int(a.roi[0]), a.roi[1])
     details = {}
+    facing = {"radius": a.facing_radius, "floor": a.facing_floor} if a.facing else None
     t0 = time.time()
     rows = evaluate_view_dependent(a.experiment, model, data, a.q_a, a.q_g, dev, a.out, view=view if a.mvub else a.view, H=a.height,
-                                   W=a.width, gradient=gradient, roi=roi, save_images=True, details=details)
+                                   W=a.width, gradient=gradient, roi=roi, save_images=True, details=details, facing=facing)
     t_all = time.time() - t0
     path = os.path.join(a.out, a.experiment, "view_dep.csv")
     with open(path, "w", newline="") as f:
@@ -74,6 +80,8 @@ def main():
     for key, row in rows.items():
         print("%-8s bpp %.4f  view psnr %.3f dB  view ssim %.5f" % (key, row["bpp"], row["psnr"], row["ssim"]))
     result = {"frame": a.frame, "n_points": int(pts.shape[0]), "H": a.height, "W": a.width, "view": a.view, "t_three_rows_s": t_all}
+    if a.facing:
+        result["t_four_rows_s"] = result.pop("t_three_rows_s")
     if a.repeat > 0:
         src, ref_img = details["source"]
         rec, img = details["uniform"]
