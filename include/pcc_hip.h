@@ -326,7 +326,11 @@ int pcc_compact_rows(const uint8_t* mask, int64_t n, const int32_t* coords, int3
  * Per-batch top-k on one logit per row (GenerativeUpBlock._topk_prediction,
  * model/blocks.py:130-150, torch.topk).  Row i belongs to batch coords[i*4]; batch b keeps
  * its k[b] largest logits (logits[i*ld]); exact ties are broken by ascending voxel key.
- * NaN sorts above +inf (torch.topk).  state: >= pcc_topk_state_elems(nbatch) int32 elements (per item the selection's words and a
+ * NaN sorts above +inf (torch.topk); -0 equals +0.  Batch b keeps max(0, min(k[b], rows of b)) rows; rows whose batch index
+ * is outside [0, nbatch) are never selected and never counted.
+ * Precondition of nbatch == 1: EVERY row belongs to batch 0.  The passes over the logit bytes then do not read the
+ * coordinates: a row with another index would be counted there and never selected, so fewer than k rows would come out.
+ * state: >= pcc_topk_state_elems(nbatch) int32 elements (per item the selection's words and a
  * 256-bin histogram; for one item also the 256 x 256 per-workgroup bins of the logit passes).
  * ------------------------------------------------------------------------------------- */
 int64_t pcc_topk_state_elems(int32_t nbatch);

@@ -42,7 +42,8 @@ def topk_mask(pred, k):
     """blocks.py:130-150 — per-batch top-k on channel 0.
 
     torch.topk leaves ties unspecified; the oracle (and the HIP path) break
-    exact ties by ascending canonical coordinate key.
+    exact ties by ascending canonical coordinate key.  The logits are ordered by
+    oc.float_key: NaN above +inf (as torch.topk puts it), -0 equal to +0.
     """
     logits = pred.F[:, 0].detach().numpy()
     keys = oc.pack(pred.C)
@@ -51,8 +52,8 @@ def topk_mask(pred, k):
     for bi, batch in enumerate(np.unique(b)):
         rows = np.nonzero(b == batch)[0]
         kk = int(k[int(batch)]) if len(k) > int(batch) else int(k[bi])
-        kk = min(kk, rows.size)
-        order = np.lexsort((keys[rows], -logits[rows].astype(np.float64)))
+        kk = max(0, min(kk, rows.size))
+        order = np.lexsort((keys[rows], -oc.float_key(logits[rows]).astype(np.int64)))
         mask[rows[order[:kk]]] = True
     return mask
 

@@ -38,6 +38,17 @@ def pack(coords):
             | ((c[:, 2] + _OFF).astype(u) << u(_BITS)) | (c[:, 3] + _OFF).astype(u))          # uint64: batch 512+ sets bit 63
 
 
+def float_key(v):
+    """uint32 key whose ascending order is the documented order of the top-k logits (include/pcc_hip.h, torch.topk): the
+    order-preserving map of the fp32 bits, -0 folded to +0, every NaN (either sign, any payload) on top at 0xFFFFFFFF."""
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    u = v.view(np.uint32).copy()
+    u[v == 0] = 0
+    key = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+    key[np.isnan(v)] = np.uint32(0xFFFFFFFF)
+    return key
+
+
 def unpack(keys):
     k = np.asarray(keys, dtype=np.uint64)
     m = np.uint64((1 << _BITS) - 1)
