@@ -148,6 +148,41 @@ int64_t pcc_color_jitter_scratch_bytes(int64_t n, int32_t nbatch);
 int pcc_color_jitter(const float* rgb, int64_t n, const int64_t* offsets, int32_t nbatch, const float* params,
                      const int32_t* order, float* out, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Voxelisation: raw points onto a voxel grid, with exact per-voxel attribute sums (the data front-end:
+ * float PLYs, scans whose points collide on the grid, re-quantisation to fewer bits; the reference
+ * down-samples its "QA" sequences through open3d's voxel_down_sample, data/utils/RawLoader.py:48-57).
+ * xyz: float32 [n,3]; batch: int32 [n] or NULL (every point in item 0); attr: float32 [n,c] or NULL when
+ * c = 0 (c = 0 .. 16).
+ *   Cell.   Per axis g = (p - origin) / voxel, then floorf(g) (rounding 0) or rintf(g) (rounding 1, ties to
+ *           even).  Every operation is rounded separately in fp32 and the division is a true, correctly
+ *           rounded division, never a multiplication by a reciprocal: numpy's float32
+ *           np.floor((p - o) / v) reproduces it bit for bit.  The grid is anchored at `origin`.
+ *   Range.  A g that is not finite or lies beyond PCC_COORD_LIMIT is never converted to an integer.  Such a
+ *           point, a batch index outside 0 .. nbatch-1, or an attribute that is not finite or has |a| > 1
+ *           makes *out_count = PCC_COUNT_ERR_RANGE (the outputs are then unspecified).  voxel <= 0, not
+ *           finite or NaN, a non-finite origin, c outside 0 .. 16, rounding other than 0 / 1, nbatch outside
+ *           1 .. PCC_BATCH_LIMIT + 1, a capacity that is no power of two or below 2 n (pcc_hash_capacity(n) is one that fits), and
+ *           null pointers are PCC_ERR_ARG, raised on the host before any launch.
+ *   Order.  Output row r is the r-th distinct (batch, cell) in input order: out_coords int32 [n,4] (room for n
+ *           rows, *out_count used), out_first[r] = the lowest input row that falls in it, out_row[i] = the
+ *           output row of point i.  Equal cells of two batch items never merge.  On return (keys, vals, cap)
+ *           is the hash table of the OUTPUT set with tensor stride 1, as after pcc_augment_rotate.
+ *   Sums.   Each attribute is converted once to Q32 fixed point, q = llrint((double)a * 4294967296.0) (ties
+ *           to even): a = k/255 is represented exactly, only values below 2^-8 round at all, by at most
+ *           2^-33.  out_sum int64 [n,c]: per voxel and channel the int64 sum of the q; out_npts int32 [n]:
+ *           the number of points.  With |a| <= 1 and n < 2^31 no sum overflows.  Integer addition commutes:
+ *           any schedule gives the same bytes (integer atomics, no float atomics).
+ *   Mean.   Left to the caller: float32(float64(sum) / float64(npts) / 2^32).
+ * The call initialises everything it accumulates into (rows 0 .. count-1 of out_npts / out_sum): buffers
+ * may be handed over uninitialised; rows behind the count are not written.  scratch: int32
+ * [pcc_scan_scratch_elems(n)].  Eight launches (clear, claim, flag, three scan kernels, finalize,
+ * accumulate); n = 0 is valid (*out_count = 0). */
+int pcc_voxelize(const float* xyz, const int32_t* batch, int64_t n, int32_t nbatch, const float* attr, int32_t c,
+                 float origin_x, float origin_y, float origin_z, float voxel, int32_t rounding, uint64_t* keys,
+                 int32_t* vals, int64_t cap, int32_t* scratch, int32_t* out_coords, int32_t* out_first,
+                 int32_t* out_npts, int64_t* out_sum, int32_t* out_row, int64_t* out_count, void* stream);
+
 /* Kernel map (ME kernel_map, cached per coordinate manager): for every output row j and
  * kernel offset k, nbr[j*K + k] = input row at c_out + sign * off_k * step, or -1.
  * sign = +1 for (strided) convolution with step = input tensor stride; sign = -1 for

@@ -21,6 +21,7 @@ from .transforms import AnalysisTransform, SparseSynthesisTransform  # noqa: F40
 from .entropy_models import MeanScaleHyperprior, MeanScaleHyperprior_Map  # noqa: F401
 from .model import ColorModel  # noqa: F401
 from .normals import estimate_normals  # noqa: F401
+from .voxelize import voxelize, downsample, Voxelized  # noqa: F401
 from . import synthetic, utils, parallel, render, augment  # noqa: F401
 
-__all__ = ["ColorModel", "SparseTensor", "CoordMap", "build", "lib", "estimate_normals"]
+__all__ = ["ColorModel", "SparseTensor", "CoordMap", "build", "lib", "estimate_normals", "voxelize", "downsample", "Voxelized"]

@@ -32,6 +32,9 @@ SIGNATURES = {
     "pcc_color_jitter_chunk": (c_i32, []),
     "pcc_color_jitter_scratch_bytes": (c_i64, [c_i64, c_i32]),
     "pcc_color_jitter": (c_int, [c_void_p, c_i64, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "pcc_voxelize": (c_int, [c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_i32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                             c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p]),
     "pcc_kernel_map": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pcc_pair_count": (c_int, [c_void_p, c_i64, c_void_p, c_void_p]),
     "pcc_conv_packed_elems": (c_i64, [c_i32, c_i32, c_i32]),
@@ -127,6 +130,7 @@ def build(force=False):
     check_kernel_resources(os.path.join(_HERE, "build", "chconv.resources.txt"), CHCONV_KERNELS)
     check_kernel_resources(os.path.join(_HERE, "build", "augment.resources.txt"), AUGMENT_KERNELS)
     check_kernel_resources(os.path.join(_HERE, "build", "normals.resources.txt"), NORMALS_KERNELS)
+    check_kernel_resources(os.path.join(_HERE, "build", "voxelize.resources.txt"), VOXELIZE_KERNELS)
     check_small_kernel_lds_reads()
     return SO_PATH
 
@@ -149,6 +153,10 @@ AUGMENT_KERNELS = ("jitter_partial_kernel", "jitter_mean_kernel", "jitter_apply_
 # the surface normals (csrc/normals.hip): the 3 x 3 Jacobi iteration runs over named scalars, and an indexed (scratch) copy of the
 # matrix would put a memory round trip into every one of its 36 rotations
 NORMALS_KERNELS = ("estimate_normals_kernel",)
+# the voxelisation (csrc/voxelize.hip): the channel loops run over a run-time count out of a handful of registers; an indexed
+# (scratch) copy of a point's channels would sit in front of every atomic of the accumulation pass
+VOXELIZE_KERNELS = ("voxelize_clear_kernel", "voxelize_insert_kernel", "voxelize_flag_kernel", "voxelize_finalize_kernel",
+                    "voxelize_accumulate_kernel")
 
 
 def check_small_kernel_lds_reads(obj=None):

@@ -14,6 +14,7 @@
 // summation shape depend on the position inside the item only — an item gives the same bytes alone and inside a batch.
 #include "common.h"
 #include "sort.h"
+#include "table_claim.h"
 
 namespace pcc {
 
@@ -195,7 +196,7 @@ __global__ __launch_bounds__(JIT_BLOCK) void jitter_apply_kernel(const float* __
 // The scheme is the coordinate manager's (coords.hip, unique_coords): claim the candidate's slot in the hashed-voxel table, atomicMin
 // the candidate index into the slot's value, flag the winners, scan the flags, and let every winner write its output row and
 // turn its slot's value into the row id — so the result does not depend on thread arrival order and the table indexes the output
-// set on return.  It lives here, with its own copy of the slot claim, because coords.hip is part of the kernel-source stamp of the
+// set on return.  It lives here, with the slot claim of table_claim.h, because coords.hip is part of the kernel-source stamp of the
 // benchmark's committed HBM-traffic profile (bench.py, kernel_source_sha256): the rotation must not make that profile stale.  The
 // slot walk is table_find's (common.h), slot for slot: the key's lane first (every 8th slot), then slot by slot.  Always the
 // seven-launch form (clear, insert, flag, three scan kernels, finalize); the scan and the count word are coords.hip's scan_flags.
@@ -234,32 +235,6 @@ __global__ __launch_bounds__(256) void rotate_clear_kernel(uint64_t* __restrict_
     }
 }
 
-// claim (or find) the slot of `key`: the mirror image of table_find.  With cap >= 2 * candidates a free slot exists, so the second
-// loop always returns; mask + 1 is unreachable and the callers still guard it.
-__device__ __forceinline__ uint64_t rotate_claim(uint64_t* keys, uint64_t mask, uint64_t key) {
-    const uint64_t slot0 = table_slot0(key, mask, 0);
-    uint64_t slot = slot0;
-    for (uint64_t probe = 0; probe <= mask; probe += TABLE_PROBE_STEP) {
-        uint64_t cur = keys[slot];
-        if (cur == KEY_EMPTY) {
-            cur = (uint64_t)atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)KEY_EMPTY, (unsigned long long)key);
-            if (cur == KEY_EMPTY) return slot;
-        }
-        if (cur == key) return slot;
-        slot = (slot + TABLE_PROBE_STEP) & mask;
-    }
-    for (uint64_t probe = 1; probe <= mask; ++probe) {
-        slot = (slot0 + probe) & mask;
-        uint64_t cur = keys[slot];
-        if (cur == KEY_EMPTY) {
-            cur = (uint64_t)atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)KEY_EMPTY, (unsigned long long)key);
-            if (cur == KEY_EMPTY) return slot;
-        }
-        if (cur == key) return slot;
-    }
-    return mask + 1;
-}
-
 __global__ __launch_bounds__(256) void rotate_insert_kernel(Rotation gen, int64_t m, uint64_t* __restrict__ keys,
                                                             int32_t* __restrict__ vals, uint64_t mask,
                                                             int32_t* __restrict__ slot_of, int32_t* __restrict__ err) {
@@ -271,7 +246,7 @@ __global__ __launch_bounds__(256) void rotate_insert_kernel(Rotation gen, int64_
         slot_of[i] = (int32_t)(mask + 1);
         return;
     }
-    const uint64_t slot = rotate_claim(keys, mask, pack_key(c.x, c.y, c.z, c.w));
+    const uint64_t slot = table_claim_slot(keys, mask, pack_key(c.x, c.y, c.z, c.w));
     slot_of[i] = (int32_t)slot;
     if (slot <= mask) atomicMin(&vals[slot], (int32_t)i);
 }

@@ -1,0 +1,196 @@
+// Voxelisation: N points (float xyz, optional batch index, optional C attribute channels) onto a voxel grid -> the distinct voxels
+// in order of first appearance, per voxel the point count and the EXACT sum of its attributes (Q32 fixed point in int64), per
+// point its voxel row.  The arithmetic is the contract of include/pcc_hip.h (pcc_voxelize): per axis (p - origin) / voxel, every
+// operation rounded separately in fp32 (the file is compiled with -ffp-contract=off; the division is hipcc's default correctly
+// rounded one, not a multiplication by a reciprocal), then floorf or rintf.  A quotient that is not finite or lies beyond the key
+// range is never converted to an integer.
+//
+// The coordinate set is built by the rotation's scheme (augment.hip): clear, claim the slot and atomicMin the candidate index, flag
+// the winners, scan the flags (coords.hip's scan_flags: three kernels and the count word), and let every winner write its row, zero
+// its accumulators and turn its slot's value into the row id.  Then ONE accumulation pass over the points: row = vals[slot_of[i]],
+// integer atomic adds into out_npts / out_sum.  Integer addition commutes, so the bytes do not depend on the schedule; there is no
+// float atomic anywhere.  Clouds arrive spatially coherent, and many adders on one destination serialise, so a wave first folds
+// every run of consecutive lanes with the same row into its first lane (a segmented shuffle reduction, skipped by a wave-uniform
+// branch when no two neighbouring lanes share a row) and only run heads issue atomics.  Eight launches.
+#include "common.h"
+#include "sort.h"
+#include "table_claim.h"
+
+namespace pcc {
+
+constexpr int VOX_BLOCK = 256;
+constexpr int VOX_MAX_CHANNELS = 16;
+
+struct Voxelizer {
+    const float* xyz;         // [n, 3]
+    const int32_t* batch;     // [n] or null = item 0
+    int nbatch;
+    float ox, oy, oz, voxel;
+    int rounding;             // 0 floorf, 1 rintf (ties to even)
+    static constexpr int REJECT = 1 << 30;
+    __device__ __forceinline__ int cell(float p, float o) const {
+        const float g = (p - o) / voxel;
+        const float r = rounding ? rintf(g) : floorf(g);
+        return (fabsf(r) <= (float)COORD_LIMIT) ? (int)r : REJECT;      // false for NaN and infinities
+    }
+    __device__ __forceinline__ int4 get(int64_t i) const {
+        const int b = batch ? batch[i] : 0;
+        if ((unsigned)b >= (unsigned)nbatch) return make_int4(-1, REJECT, REJECT, REJECT);
+        return make_int4(b, cell(xyz[3 * i], ox), cell(xyz[3 * i + 1], oy), cell(xyz[3 * i + 2], oz));
+    }
+};
+
+__global__ __launch_bounds__(VOX_BLOCK) void voxelize_clear_kernel(uint64_t* __restrict__ keys, int32_t* __restrict__ vals, int64_t cap,
+                                                                   int32_t* __restrict__ err) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *err = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (int64_t)gridDim.x * blockDim.x) {
+        keys[i] = KEY_EMPTY;
+        vals[i] = 0x7fffffff;
+    }
+}
+
+// a point with a cell out of range, a batch index without an item or an attribute that is not finite or exceeds 1 in magnitude
+// raises the error word and takes no part in the set (slot_of = mask + 1)
+__global__ __launch_bounds__(VOX_BLOCK) void voxelize_insert_kernel(Voxelizer gen, int64_t n, const float* __restrict__ attr, int c,
+                                                                    uint64_t* __restrict__ keys, int32_t* __restrict__ vals,
+                                                                    uint64_t mask, int32_t* __restrict__ slot_of,
+                                                                    int32_t* __restrict__ err) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int4 v = gen.get(i);
+    bool ok = coord_in_range(v.x, v.y, v.z, v.w);
+    for (int ch = 0; ch < c; ++ch) ok = ok && (fabsf(attr[i * c + ch]) <= 1.0f);      // false for NaN
+    if (!ok) {
+        *err = 1;
+        slot_of[i] = (int32_t)(mask + 1);
+        return;
+    }
+    const uint64_t slot = table_claim_slot(keys, mask, pack_key(v.x, v.y, v.z, v.w));
+    slot_of[i] = (int32_t)slot;
+    if (slot <= mask) atomicMin(&vals[slot], (int32_t)i);
+}
+
+__global__ __launch_bounds__(VOX_BLOCK) void voxelize_flag_kernel(int64_t n, const int32_t* __restrict__ vals, uint32_t mask,
+                                                                  const int32_t* __restrict__ slot_of, int32_t* __restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t slot = (uint32_t)slot_of[i];
+    flags[i] = (slot <= mask && vals[slot] == (int32_t)i) ? 1 : 0;       // slot > mask: the point was rejected (range error)
+}
+
+// incl = inclusive scan of the winner flags: point i won iff the scan steps at i, and its output row is incl[i] - 1.  The winner
+// also zeroes the accumulators of its row: the caller hands over uninitialised buffers, and only the rows in use are touched.
+__global__ __launch_bounds__(VOX_BLOCK) void voxelize_finalize_kernel(Voxelizer gen, int64_t n, int c, int32_t* __restrict__ vals,
+                                                                      const int32_t* __restrict__ slot_of,
+                                                                      const int32_t* __restrict__ incl, int32_t* __restrict__ out_coords,
+                                                                      int32_t* __restrict__ out_first, int32_t* __restrict__ out_npts,
+                                                                      int64_t* __restrict__ out_sum) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t cur = incl[i], prev = i ? incl[i - 1] : 0;
+    if (cur != prev) {
+        const int32_t row = cur - 1;
+        reinterpret_cast<int4*>(out_coords)[row] = gen.get(i);
+        out_first[row] = (int32_t)i;
+        out_npts[row] = 0;
+        for (int ch = 0; ch < c; ++ch) out_sum[(int64_t)row * c + ch] = 0;
+        vals[slot_of[i]] = row;
+    }
+}
+
+// sum of v over lanes [lane, end) of the wave, `end` = one past the last lane of this lane's run; every lane takes part
+__device__ __forceinline__ int64_t run_sum(int64_t v, int lane, int end) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int64_t o = __shfl_down(v, d, 64);
+        if (lane + d < end) v += o;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(VOX_BLOCK) void voxelize_accumulate_kernel(int64_t n, const float* __restrict__ attr, int c,
+                                                                        const int32_t* __restrict__ vals, uint32_t mask,
+                                                                        const int32_t* __restrict__ slot_of, int32_t* __restrict__ out_row,
+                                                                        int32_t* __restrict__ out_npts, int64_t* __restrict__ out_sum) {
+    // (no early return: the lanes behind the last point of a ragged wave take part in the shuffles, as runs of their own)
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int32_t row = -1;                                  // no point, or a rejected one: adds nothing
+    if (i < n) {
+        const uint32_t slot = (uint32_t)slot_of[i];
+        if (slot <= mask) row = vals[slot];
+        out_row[i] = row;
+    }
+    const int32_t before = __shfl_up(row, 1, 64);
+    const bool head = lane == 0 || before != row || row < 0;
+    const uint64_t heads = __ballot(head);
+    if (heads == ~0ull) {                              // wave-uniform: no two neighbouring lanes share a row
+        if (row >= 0) {
+            atomicAdd(&out_npts[row], 1);
+            for (int ch = 0; ch < c; ++ch) {
+                const int64_t q = llrint((double)attr[i * c + ch] * 4294967296.0);
+                atomicAdd(reinterpret_cast<unsigned long long*>(&out_sum[(int64_t)row * c + ch]), (unsigned long long)q);
+            }
+        }
+        return;
+    }
+    const uint64_t above = lane == 63 ? 0ull : (heads >> (lane + 1));
+    const int end = above ? lane + 1 + __builtin_ctzll(above) : 64;      // the next head, or the end of the wave
+    const bool adds = head && row >= 0;
+    if (adds) atomicAdd(&out_npts[row], end - lane);
+    for (int ch = 0; ch < c; ++ch) {
+        const int64_t q = row >= 0 ? llrint((double)attr[i * c + ch] * 4294967296.0) : 0;
+        const int64_t s = run_sum(q, lane, end);
+        if (adds) atomicAdd(reinterpret_cast<unsigned long long*>(&out_sum[(int64_t)row * c + ch]), (unsigned long long)s);
+    }
+}
+
+}  // namespace pcc
+
+using namespace pcc;
+
+extern "C" {
+
+int pcc_voxelize(const float* xyz, const int32_t* batch, int64_t n, int32_t nbatch, const float* attr, int32_t c, float ox, float oy,
+                 float oz, float voxel, int32_t rounding, uint64_t* keys, int32_t* vals, int64_t cap, int32_t* scratch,
+                 int32_t* out_coords, int32_t* out_first, int32_t* out_npts, int64_t* out_sum, int32_t* out_row, int64_t* out_count,
+                 void* stream) {
+    PCC_REQUIRE(n >= 0 && n < (1ll << 31) - 1, "pcc_voxelize: bad point count %lld", (long long)n);
+    PCC_REQUIRE(nbatch >= 1 && nbatch <= BATCH_LIMIT + 1, "pcc_voxelize: nbatch %d outside 1..%d", nbatch, BATCH_LIMIT + 1);
+    PCC_REQUIRE(c >= 0 && c <= VOX_MAX_CHANNELS, "pcc_voxelize: %d attribute channels outside 0..%d", c, VOX_MAX_CHANNELS);
+    PCC_REQUIRE(voxel > 0.0f && voxel <= 3.0e38f, "pcc_voxelize: the voxel size must be a positive finite number (got %g)", (double)voxel);
+    PCC_REQUIRE(ox - ox == 0.0f && oy - oy == 0.0f && oz - oz == 0.0f, "pcc_voxelize: the origin is not finite");
+    PCC_REQUIRE(rounding == 0 || rounding == 1, "pcc_voxelize: rounding %d is neither 0 (floor) nor 1 (nearest, ties to even)", rounding);
+    PCC_REQUIRE(cap > 0 && (cap & (cap - 1)) == 0 && cap >= 2 * n && cap <= (1ll << 31), "pcc_voxelize: bad capacity %lld for n=%lld",
+                (long long)cap, (long long)n);
+    PCC_REQUIRE(keys && vals && scratch && out_count, "pcc_voxelize: null table, scratch or count");
+    PCC_REQUIRE(n == 0 || (xyz && out_coords && out_first && out_npts && out_row), "pcc_voxelize: null points or outputs");
+    PCC_REQUIRE(n == 0 || c == 0 || (attr && out_sum), "pcc_voxelize: null attributes or sums with c = %d", c);
+    hipStream_t st = as_stream(stream);
+    // scratch as pcc_scan_scratch_elems(n) lays it out: slot per point, flags, the scan's block sums, then the error word
+    int32_t* slot_of = scratch;
+    int32_t* flags = scratch + n;
+    int32_t* block_sums = scratch + 2 * n;
+    int32_t* err = block_sums + (scan_block_sums_elems(n) - 16) + 8;
+    hipLaunchKernelGGL(voxelize_clear_kernel, dim3(blocks_for(cap, VOX_BLOCK, 4096)), dim3(VOX_BLOCK), 0, st, keys, vals, cap, err);
+    if (n == 0) {
+        PCC_CHECK_HIP(hipMemsetAsync(out_count, 0, sizeof(int64_t), st));
+        return PCC_OK;
+    }
+    const Voxelizer gen{xyz, batch, nbatch, ox, oy, oz, voxel, rounding};
+    const unsigned nb = blocks_for(n, VOX_BLOCK);
+    const uint64_t mask = (uint64_t)(cap - 1);
+    hipLaunchKernelGGL(voxelize_insert_kernel, dim3(nb), dim3(VOX_BLOCK), 0, st, gen, n, attr, c, keys, vals, mask, slot_of, err);
+    hipLaunchKernelGGL(voxelize_flag_kernel, dim3(nb), dim3(VOX_BLOCK), 0, st, n, (const int32_t*)vals, (uint32_t)mask, (const int32_t*)slot_of,
+                       flags);
+    const int rc = scan_flags(flags, n, flags, block_sums, out_count, 1, st, err);
+    if (rc) return rc;
+    hipLaunchKernelGGL(voxelize_finalize_kernel, dim3(nb), dim3(VOX_BLOCK), 0, st, gen, n, c, vals, (const int32_t*)slot_of,
+                       (const int32_t*)flags, out_coords, out_first, out_npts, out_sum);
+    hipLaunchKernelGGL(voxelize_accumulate_kernel, dim3(nb), dim3(VOX_BLOCK), 0, st, n, attr, c, (const int32_t*)vals, (uint32_t)mask,
+                       (const int32_t*)slot_of, out_row, out_npts, out_sum);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+}  // extern "C"

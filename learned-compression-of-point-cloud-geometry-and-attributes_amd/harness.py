@@ -63,9 +63,39 @@ def compress_model_ours(experiment, model, data, q_a, q_g, device, base_path):
     return source, reconstruction, bpp, t_compress, t_decompress
 
 
-def evaluate_frame(experiment, model, data, q_a, q_g, device, base_path, resolution=1023, d2_radius=None):
+def downsample_frame(data, factor, device, q_a=None, q_g=None):
+    """the frame ``data`` on a grid ``factor`` times coarser (voxelize.downsample: cell indices, exact mean colours) ->
+    (data', q_a', q_g'); per-point quality arrays follow their voxel's first point, scalars pass through"""
+    from .voxelize import voxelize
+    points = data["src"]["points"][0].to(device, dtype=torch.float)
+    colors = data["src"]["colors"][0].to(device, dtype=torch.float)
+    v = voxelize(points, colors, voxel_size=factor)
+
+    def follow(q):
+        if q is None or isinstance(q, (float, int, np.floating)):
+            return q
+        return torch.as_tensor(q).reshape(points.shape[0], 1).to(device)[v.first.long()]
+
+    small = dict(data)
+    small["src"] = dict(data["src"], points=v.coords[None, :, 1:].to(torch.float), colors=v.features[None])
+    return small, follow(q_a), follow(q_g)
+
+
+def evaluate_frame(experiment, model, data, q_a, q_g, device, base_path, resolution=1023, d2_radius=None, downsample=None):
     """one row of the sweep table (evaluate.py:100-160): rate, times, D1 and colour PSNRs; with ``d2_radius`` (the radius of the
-    normal estimation, in voxels) also ``sym_d2_psnr``, the point-to-plane figure of utils.py:263-288"""
+    normal estimation, in voxels) also ``sym_d2_psnr``, the point-to-plane figure of utils.py:263-288.
+
+    ``downsample`` (a factor, e.g. 2, 4, 8: the reference's "QA" sequences, data/utils/RawLoader.py:48-57): the frame is first
+    voxelised on a grid that many times coarser (downsample_frame); source and quality map are built on the down-sampled
+    cloud, the metrics are taken against it, and ``resolution`` (the peak of the geometry PSNR, 2^bits - 1) is scaled to the
+    coarser grid: (resolution + 1) / factor - 1.  The row gains ``downsample`` and ``n_input``, the frame's own point count."""
+    n_input = None
+    if downsample is not None:
+        if not float(downsample) >= 1.0:
+            raise ValueError(f"downsample {downsample}: a factor of at least 1")
+        n_input = int(data["src"]["points"].shape[1])
+        data, q_a, q_g = downsample_frame(data, downsample, device, q_a, q_g)
+        resolution = max(1, int(round((resolution + 1) / float(downsample))) - 1)
     src, rec, bpp, t_c, t_d = compress_model_ours(experiment, model, data, q_a, q_g, device, base_path)
     metric = PointCloudMetric(src, rec, resolution=resolution, device=device)
     res, _ = metric.compute_pointcloud_metrics(drop_duplicates=True)
@@ -75,6 +105,8 @@ def evaluate_frame(experiment, model, data, q_a, q_g, device, base_path, resolut
             "sym_v_psnr": res["sym_v_psnr"]}
     if d2_radius is not None:
         row["sym_d2_psnr"] = metric.compute_d2(radius=d2_radius)["sym_d2_psnr"]
+    if downsample is not None:
+        row["downsample"], row["n_input"] = float(downsample), n_input
     return row
 
 

@@ -6,7 +6,10 @@ Seeded random weights in their q-RESPONSIVE variant (synthetic.FILM_GAIN_Q_RESPO
 follows the quality map; PCC_SWEEP_FILM_GAIN overrides): the rate axis is a real sweep, the distortion axis is that of random
 weights — not codec quality.
 
-usage: rd_sweep.py [--d2 R] [out.json] [weights.pt]     (--d2 R: add the point-to-plane PSNR, normals over R voxels)"""
+usage: rd_sweep.py [--d2 R] [--downsample F] [out.json] [weights.pt]
+  --d2 R: add the point-to-plane PSNR, normals over R voxels
+  --downsample F: code every frame on a grid F times coarser (pcc_amd.voxelize: exact mean colours; the reference's "QA" factors
+                  are 1, 2, 4, 8), metrics against the down-sampled source"""
 import json, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -22,6 +25,11 @@ if "--d2" in sys.argv:
     at = sys.argv.index("--d2")
     d2_radius = int(sys.argv[at + 1])
     del sys.argv[at:at + 2]
+downsample = None
+if "--downsample" in sys.argv:
+    at = sys.argv.index("--downsample")
+    downsample = float(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
 FRAMES = {"redandblack~": 247.0, "loot~": 255.0, "longdress~": 261.5, "soldier~": 294.5}   # shell radii -> ~0.76 / 0.81 / 0.86 / 1.09 M
 QS = [(0.05, 0.1), (0.1, 0.2), (0.2, 0.4), (0.4, 0.8)]
 film_gain = float(os.environ.get("PCC_SWEEP_FILM_GAIN", syn.FILM_GAIN_Q_RESPONSIVE))
@@ -36,7 +44,7 @@ with tempfile.TemporaryDirectory() as td:
         data = {"src": {"points": torch.from_numpy(pts[None, :, :3]), "colors": torch.from_numpy(pts[None, :, 3:])}}
         for q_g, q_a in QS:
             t0 = time.time()
-            row = evaluate_frame("sweep", model, data, q_a, q_g, dev, td, d2_radius=d2_radius)
+            row = evaluate_frame("sweep", model, data, q_a, q_g, dev, td, d2_radius=d2_radius, downsample=downsample)
             row["frame"] = name
             rows.append(row)
             print(f"{name:13s} N={row['n_source']:8d} q=({q_g},{q_a}) bpp {row['bpp']:.3f} D1 {row['sym_p2p_psnr']:.2f} Y {row['sym_y_psnr']:.2f} "

@@ -28,6 +28,9 @@ def main():
     ap.add_argument("--log-every", type=int, default=20)
     ap.add_argument("--augment", action="store_true",
                     help="ColorJitter + RandomRotate on every batch, on the device (pcc_amd.augment.TrainAugment; configs/Ours.yaml:29-35)")
+    ap.add_argument("--voxel-size", type=float, default=None,
+                    help="voxelise every --ply cloud on a grid of this pitch before slicing (pcc_amd.voxelize: cell indices, exact mean "
+                         "colours), so PLYs with float positions or colliding points train instead of failing")
     args = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
@@ -51,6 +54,9 @@ def main():
 
     clouds = [io.read_ply(p) for p in args.ply] if args.ply else \
              [syn.sphere_shell(grid=1024, radius=r, half_width=0.5, noise=0.02, seed=i) for i, r in enumerate((180.0, 230.0, 260.0))]
+    if args.voxel_size is not None and args.ply:
+        clouds = [pcc_amd.downsample(torch.from_numpy(np.ascontiguousarray(c[:, :6], dtype=np.float32)).to(dev), args.voxel_size).cpu().numpy()
+                  for c in clouds]
     cubes = []
     for c in clouds:
         _, rows = par.split_blocks(c, args.block)
