@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
-from .sparse import _host_count, _read_count, _require_cuda, gather_rows
+from .sparse import _host_count, _read_count, _require_cuda, _set_buffers, gather_rows
 
 BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3          # operation codes of ``order`` (torchvision's fn_idx)
 
@@ -64,21 +64,17 @@ def _rotate(C, matrices, block_size):
     dev = C.device
     rot = _to_device(matrices, torch.float32, dev).reshape(-1, 9)
     nbatch, n = rot.shape[0], C.shape[0]
-    L = _lib.lib()
-    cap = L.pcc_hash_capacity(n)
-    keys = torch.empty(cap, dtype=torch.int64, device=dev)
-    vals = torch.empty(cap, dtype=torch.int32, device=dev)
-    scratch = torch.empty(L.pcc_scan_scratch_elems(n), dtype=torch.int32, device=dev)
+    keys, vals, cap, scratch = _set_buffers(n, dev)
     out = torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev)
     src = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     count, word = _host_count()
-    check(L.pcc_augment_rotate(ptr(C), n, ptr(rot), nbatch, float(block_size) / 2.0, ptr(keys), ptr(vals), cap, ptr(scratch),
-                               ptr(out), ptr(src), ptr(count), _lib.stream()))
+    check(_lib.lib().pcc_augment_rotate(ptr(C), n, ptr(rot), nbatch, float(block_size) / 2.0, ptr(keys), ptr(vals), cap, ptr(scratch),
+                                        ptr(out), ptr(src), ptr(count), _lib.stream()))
     m = _read_count(word, dev)
     return out[:m], src[:m], (keys, vals, cap)
 
 
-BATCH_SLOTS = 1023                                          # PCC_BATCH_LIMIT + 1 (include/pcc_hip.h)
+BATCH_SLOTS = _lib.PCC.BATCH_LIMIT + 1                      # every index the voxel key can hold
 
 
 def _offsets_of(C, nbatch=None):

@@ -13,8 +13,7 @@
 // No float atomics: the mean is a fixed-shape sum, so results are bitwise equal from run to run, and — chunk boundaries and
 // summation shape depend on the position inside the item only — an item gives the same bytes alone and inside a batch.
 #include "common.h"
-#include "sort.h"
-#include "table_claim.h"
+#include "first_rows.h"
 
 namespace pcc {
 
@@ -191,15 +190,8 @@ __global__ __launch_bounds__(JIT_BLOCK) void jitter_apply_kernel(const float* __
 }
 
 // ---------------------------------------------------------------------------------------------
-// RandomRotate: unique rotated-and-rounded rows in order of first appearance, the lowest input row wins.
-//
-// The scheme is the coordinate manager's (coords.hip, unique_coords): claim the candidate's slot in the hashed-voxel table, atomicMin
-// the candidate index into the slot's value, flag the winners, scan the flags, and let every winner write its output row and
-// turn its slot's value into the row id — so the result does not depend on thread arrival order and the table indexes the output
-// set on return.  It lives here, with the slot claim of table_claim.h, because coords.hip is part of the kernel-source stamp of the
-// benchmark's committed HBM-traffic profile (bench.py, kernel_source_sha256): the rotation must not make that profile stale.  The
-// slot walk is table_find's (common.h), slot for slot: the key's lane first (every 8th slot), then slot by slot.  Always the
-// seven-launch form (clear, insert, flag, three scan kernels, finalize); the scan and the count word are coords.hip's scan_flags.
+// RandomRotate: unique rotated-and-rounded rows in order of first appearance, the lowest input row wins: the first-row set of
+// first_rows.h over the candidates below (seven launches).
 //
 // The arithmetic is the contract of include/pcc_hip.h: every product and sum rounded separately in fp32 (the file is compiled
 // with -ffp-contract=off), in the sum order of torch.mm(points - s/2, R.T) + s/2, then rintf (ties to even).  A result that is not
@@ -224,55 +216,14 @@ struct Rotation {
         return make_int4(c.x, grid(((dx * R[0] + dy * R[1]) + dz * R[2]) + half), grid(((dx * R[3] + dy * R[4]) + dz * R[5]) + half),
                          grid(((dx * R[6] + dy * R[7]) + dz * R[8]) + half));
     }
+    __device__ __forceinline__ bool ok(int64_t, bool ok) const { return ok; }
 };
 
-__global__ __launch_bounds__(256) void rotate_clear_kernel(uint64_t* __restrict__ keys, int32_t* __restrict__ vals, int64_t cap,
-                                                           int32_t* __restrict__ err) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *err = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (int64_t)gridDim.x * blockDim.x) {
-        keys[i] = KEY_EMPTY;
-        vals[i] = 0x7fffffff;
-    }
-}
-
-__global__ __launch_bounds__(256) void rotate_insert_kernel(Rotation gen, int64_t m, uint64_t* __restrict__ keys,
-                                                            int32_t* __restrict__ vals, uint64_t mask,
-                                                            int32_t* __restrict__ slot_of, int32_t* __restrict__ err) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const int4 c = gen.get(i);
-    if (!coord_in_range(c.x, c.y, c.z, c.w)) {
-        *err = 1;
-        slot_of[i] = (int32_t)(mask + 1);
-        return;
-    }
-    const uint64_t slot = table_claim_slot(keys, mask, pack_key(c.x, c.y, c.z, c.w));
-    slot_of[i] = (int32_t)slot;
-    if (slot <= mask) atomicMin(&vals[slot], (int32_t)i);
-}
-
-__global__ __launch_bounds__(256) void rotate_flag_kernel(int64_t m, const int32_t* __restrict__ vals, uint32_t mask,
-                                                          const int32_t* __restrict__ slot_of, int32_t* __restrict__ flags) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const uint32_t slot = (uint32_t)slot_of[i];
-    flags[i] = (slot <= mask && vals[slot] == (int32_t)i) ? 1 : 0;       // slot > mask: the candidate was rejected (range error)
-}
-
-// incl = inclusive scan of the winner flags: candidate i won iff the scan steps at i, and its output row is incl[i] - 1
-__global__ __launch_bounds__(256) void rotate_finalize_kernel(Rotation gen, int64_t m, int32_t* __restrict__ vals,
-                                                              const int32_t* __restrict__ slot_of, const int32_t* __restrict__ incl,
-                                                              int32_t* __restrict__ out_coords, int32_t* __restrict__ out_src) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const int32_t cur = incl[i], prev = i ? incl[i - 1] : 0;
-    if (cur != prev) {
-        const int32_t row = cur - 1;
-        reinterpret_cast<int4*>(out_coords)[row] = gen.get(i);
-        out_src[row] = (int32_t)i;
-        vals[slot_of[i]] = row;
-    }
-}
+// a winner records the input row it came from
+struct RotationSink {
+    int32_t* out_src;
+    __device__ __forceinline__ void operator()(int32_t row, int64_t i) const { out_src[row] = (int32_t)i; }
+};
 
 }  // namespace pcc
 
@@ -290,27 +241,8 @@ int pcc_augment_rotate(const int32_t* coords, int64_t n, const float* rot, int32
     PCC_REQUIRE(keys && vals && scratch && out_count, "pcc_augment_rotate: null table, scratch or count");
     PCC_REQUIRE(n == 0 || (coords && rot && out_coords && out_src), "pcc_augment_rotate: null rows, matrices or outputs");
     PCC_REQUIRE(half == half, "pcc_augment_rotate: half is not a number");
-    hipStream_t st = as_stream(stream);
-    // scratch as pcc_scan_scratch_elems(n) lays it out: slot per candidate, flags, the scan's block sums, then the error word
-    int32_t* slot_of = scratch;
-    int32_t* flags = scratch + n;
-    int32_t* block_sums = scratch + 2 * n;
-    int32_t* err = block_sums + (scan_block_sums_elems(n) - 16) + 8;
-    hipLaunchKernelGGL(rotate_clear_kernel, dim3(blocks_for(cap, 256, 4096)), dim3(256), 0, st, keys, vals, cap, err);
-    if (n == 0) {
-        PCC_CHECK_HIP(hipMemsetAsync(out_count, 0, sizeof(int64_t), st));
-        return PCC_OK;
-    }
-    const Rotation gen{coords, rot, nbatch, half};
-    const unsigned nb = blocks_for(n, 256);
-    hipLaunchKernelGGL(rotate_insert_kernel, dim3(nb), dim3(256), 0, st, gen, n, keys, vals, (uint64_t)(cap - 1), slot_of, err);
-    hipLaunchKernelGGL(rotate_flag_kernel, dim3(nb), dim3(256), 0, st, n, (const int32_t*)vals, (uint32_t)(cap - 1), (const int32_t*)slot_of, flags);
-    const int rc = scan_flags(flags, n, flags, block_sums, out_count, 1, st, err);
-    if (rc) return rc;
-    hipLaunchKernelGGL(rotate_finalize_kernel, dim3(nb), dim3(256), 0, st, gen, n, vals, (const int32_t*)slot_of, (const int32_t*)flags, out_coords,
-                       out_src);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    return first_rows_build(Rotation{coords, rot, nbatch, half}, RotationSink{out_src}, n, keys, vals, cap, scratch, out_coords, out_count,
+                            as_stream(stream));
 }
 
 int32_t pcc_color_jitter_chunk(void) { return JIT_CHUNK; }

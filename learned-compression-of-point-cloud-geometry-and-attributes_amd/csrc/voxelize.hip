@@ -5,16 +5,14 @@
 // rounded one, not a multiplication by a reciprocal), then floorf or rintf.  A quotient that is not finite or lies beyond the key
 // range is never converted to an integer.
 //
-// The coordinate set is built by the rotation's scheme (augment.hip): clear, claim the slot and atomicMin the candidate index, flag
-// the winners, scan the flags (coords.hip's scan_flags: three kernels and the count word), and let every winner write its row, zero
-// its accumulators and turn its slot's value into the row id.  Then ONE accumulation pass over the points: row = vals[slot_of[i]],
-// integer atomic adds into out_npts / out_sum.  Integer addition commutes, so the bytes do not depend on the schedule; there is no
+// The coordinate set is the first-row set of first_rows.h (seven launches); every winner also records its point and zeroes its
+// accumulators.  Then ONE accumulation pass over the points: row = vals[slot_of[i]], integer atomic adds into out_npts / out_sum.
+// Integer addition commutes, so the bytes do not depend on the schedule; there is no
 // float atomic anywhere.  Clouds arrive spatially coherent, and many adders on one destination serialise, so a wave first folds
 // every run of consecutive lanes with the same row into its first lane (a segmented shuffle reduction, skipped by a wave-uniform
 // branch when no two neighbouring lanes share a row) and only run heads issue atomics.  Eight launches.
 #include "common.h"
-#include "sort.h"
-#include "table_claim.h"
+#include "first_rows.h"
 
 namespace pcc {
 
@@ -24,6 +22,8 @@ constexpr int VOX_MAX_CHANNELS = 16;
 struct Voxelizer {
     const float* xyz;         // [n, 3]
     const int32_t* batch;     // [n] or null = item 0
+    const float* attr;        // [n, c]
+    int c;
     int nbatch;
     float ox, oy, oz, voxel;
     int rounding;             // 0 floorf, 1 rintf (ties to even)
@@ -38,65 +38,26 @@ struct Voxelizer {
         if ((unsigned)b >= (unsigned)nbatch) return make_int4(-1, REJECT, REJECT, REJECT);
         return make_int4(b, cell(xyz[3 * i], ox), cell(xyz[3 * i + 1], oy), cell(xyz[3 * i + 2], oz));
     }
+    // a point with a cell out of range, a batch index without an item or an attribute that is not finite or exceeds 1 in magnitude
+    // raises the error word and takes no part in the set (slot_of = mask + 1)
+    __device__ __forceinline__ bool ok(int64_t i, bool ok) const {
+        for (int ch = 0; ch < c; ++ch) ok = ok && (fabsf(attr[i * c + ch]) <= 1.0f);      // false for NaN
+        return ok;
+    }
 };
 
-__global__ __launch_bounds__(VOX_BLOCK) void voxelize_clear_kernel(uint64_t* __restrict__ keys, int32_t* __restrict__ vals, int64_t cap,
-                                                                   int32_t* __restrict__ err) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *err = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (int64_t)gridDim.x * blockDim.x) {
-        keys[i] = KEY_EMPTY;
-        vals[i] = 0x7fffffff;
-    }
-}
-
-// a point with a cell out of range, a batch index without an item or an attribute that is not finite or exceeds 1 in magnitude
-// raises the error word and takes no part in the set (slot_of = mask + 1)
-__global__ __launch_bounds__(VOX_BLOCK) void voxelize_insert_kernel(Voxelizer gen, int64_t n, const float* __restrict__ attr, int c,
-                                                                    uint64_t* __restrict__ keys, int32_t* __restrict__ vals,
-                                                                    uint64_t mask, int32_t* __restrict__ slot_of,
-                                                                    int32_t* __restrict__ err) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int4 v = gen.get(i);
-    bool ok = coord_in_range(v.x, v.y, v.z, v.w);
-    for (int ch = 0; ch < c; ++ch) ok = ok && (fabsf(attr[i * c + ch]) <= 1.0f);      // false for NaN
-    if (!ok) {
-        *err = 1;
-        slot_of[i] = (int32_t)(mask + 1);
-        return;
-    }
-    const uint64_t slot = table_claim_slot(keys, mask, pack_key(v.x, v.y, v.z, v.w));
-    slot_of[i] = (int32_t)slot;
-    if (slot <= mask) atomicMin(&vals[slot], (int32_t)i);
-}
-
-__global__ __launch_bounds__(VOX_BLOCK) void voxelize_flag_kernel(int64_t n, const int32_t* __restrict__ vals, uint32_t mask,
-                                                                  const int32_t* __restrict__ slot_of, int32_t* __restrict__ flags) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t slot = (uint32_t)slot_of[i];
-    flags[i] = (slot <= mask && vals[slot] == (int32_t)i) ? 1 : 0;       // slot > mask: the point was rejected (range error)
-}
-
-// incl = inclusive scan of the winner flags: point i won iff the scan steps at i, and its output row is incl[i] - 1.  The winner
-// also zeroes the accumulators of its row: the caller hands over uninitialised buffers, and only the rows in use are touched.
-__global__ __launch_bounds__(VOX_BLOCK) void voxelize_finalize_kernel(Voxelizer gen, int64_t n, int c, int32_t* __restrict__ vals,
-                                                                      const int32_t* __restrict__ slot_of,
-                                                                      const int32_t* __restrict__ incl, int32_t* __restrict__ out_coords,
-                                                                      int32_t* __restrict__ out_first, int32_t* __restrict__ out_npts,
-                                                                      int64_t* __restrict__ out_sum) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t cur = incl[i], prev = i ? incl[i - 1] : 0;
-    if (cur != prev) {
-        const int32_t row = cur - 1;
-        reinterpret_cast<int4*>(out_coords)[row] = gen.get(i);
+// The winner also zeroes the accumulators of its row: the caller hands over uninitialised buffers, and only the rows in use are
+// touched.
+struct VoxelSink {
+    int c;
+    int32_t *out_first, *out_npts;
+    int64_t* out_sum;
+    __device__ __forceinline__ void operator()(int32_t row, int64_t i) const {
         out_first[row] = (int32_t)i;
         out_npts[row] = 0;
         for (int ch = 0; ch < c; ++ch) out_sum[(int64_t)row * c + ch] = 0;
-        vals[slot_of[i]] = row;
     }
-}
+};
 
 // sum of v over lanes [lane, end) of the wave, `end` = one past the last lane of this lane's run; every lane takes part
 __device__ __forceinline__ int64_t run_sum(int64_t v, int lane, int end) {
@@ -167,28 +128,11 @@ int pcc_voxelize(const float* xyz, const int32_t* batch, int64_t n, int32_t nbat
     PCC_REQUIRE(n == 0 || (xyz && out_coords && out_first && out_npts && out_row), "pcc_voxelize: null points or outputs");
     PCC_REQUIRE(n == 0 || c == 0 || (attr && out_sum), "pcc_voxelize: null attributes or sums with c = %d", c);
     hipStream_t st = as_stream(stream);
-    // scratch as pcc_scan_scratch_elems(n) lays it out: slot per point, flags, the scan's block sums, then the error word
-    int32_t* slot_of = scratch;
-    int32_t* flags = scratch + n;
-    int32_t* block_sums = scratch + 2 * n;
-    int32_t* err = block_sums + (scan_block_sums_elems(n) - 16) + 8;
-    hipLaunchKernelGGL(voxelize_clear_kernel, dim3(blocks_for(cap, VOX_BLOCK, 4096)), dim3(VOX_BLOCK), 0, st, keys, vals, cap, err);
-    if (n == 0) {
-        PCC_CHECK_HIP(hipMemsetAsync(out_count, 0, sizeof(int64_t), st));
-        return PCC_OK;
-    }
-    const Voxelizer gen{xyz, batch, nbatch, ox, oy, oz, voxel, rounding};
-    const unsigned nb = blocks_for(n, VOX_BLOCK);
-    const uint64_t mask = (uint64_t)(cap - 1);
-    hipLaunchKernelGGL(voxelize_insert_kernel, dim3(nb), dim3(VOX_BLOCK), 0, st, gen, n, attr, c, keys, vals, mask, slot_of, err);
-    hipLaunchKernelGGL(voxelize_flag_kernel, dim3(nb), dim3(VOX_BLOCK), 0, st, n, (const int32_t*)vals, (uint32_t)mask, (const int32_t*)slot_of,
-                       flags);
-    const int rc = scan_flags(flags, n, flags, block_sums, out_count, 1, st, err);
-    if (rc) return rc;
-    hipLaunchKernelGGL(voxelize_finalize_kernel, dim3(nb), dim3(VOX_BLOCK), 0, st, gen, n, c, vals, (const int32_t*)slot_of,
-                       (const int32_t*)flags, out_coords, out_first, out_npts, out_sum);
-    hipLaunchKernelGGL(voxelize_accumulate_kernel, dim3(nb), dim3(VOX_BLOCK), 0, st, n, attr, c, (const int32_t*)vals, (uint32_t)mask,
-                       (const int32_t*)slot_of, out_row, out_npts, out_sum);
+    const int rc = first_rows_build(Voxelizer{xyz, batch, attr, c, nbatch, ox, oy, oz, voxel, rounding}, VoxelSink{c, out_first, out_npts, out_sum},
+                                    n, keys, vals, cap, scratch, out_coords, out_count, st);
+    if (rc || n == 0) return rc;
+    hipLaunchKernelGGL(voxelize_accumulate_kernel, dim3(blocks_for(n, VOX_BLOCK)), dim3(VOX_BLOCK), 0, st, n, attr, c, (const int32_t*)vals,
+                       (uint32_t)(cap - 1), (const int32_t*)FirstRowsScratch(scratch, n).slot_of, out_row, out_npts, out_sum);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
 }

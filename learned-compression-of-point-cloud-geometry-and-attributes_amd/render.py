@@ -32,7 +32,7 @@ from ._lib import check, ptr
 VIEWS = {"front": ((0, 0, 1), (0, 1, 0)), "side": ((-1, 0, 0), (0, 1, 0))}
 VIEWS_MVUB = {"front": ((0, -1, 0), (0, 0, 1)), "side": ((-1, 0, 0), (0, 0, 1))}
 
-COORD_LIMIT = 130000          # PCC_COORD_LIMIT (include/pcc_hip.h)
+COORD_LIMIT = _lib.PCC.COORD_LIMIT
 
 
 def _axis(v, name):

@@ -21,9 +21,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib, _threads
-from ._lib import check, ptr
+from ._lib import PCC, check, ptr
 
-ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
+ACT_NONE, ACT_RELU, ACT_LRELU = PCC.ACT_NONE, PCC.ACT_RELU, PCC.ACT_LEAKY_RELU
 
 
 def _require_cuda(t):
@@ -102,10 +102,10 @@ def set_small_paths(mask):
 
 
 class CoordinateRangeError(ValueError):
-    """a coordinate outside the voxel key's range (|c| <= 130000, 0 <= batch index <= 1022: include/pcc_hip.h)"""
+    """a coordinate outside the voxel key's range (|c| <= PCC_COORD_LIMIT, 0 <= batch index <= PCC_BATCH_LIMIT: include/pcc_hip.h)"""
 
 
-COUNT_ARMED, COUNT_ERR_RANGE = -1, -2            # PCC_COUNT_ERR_RANGE of include/pcc_hip.h
+COUNT_ARMED, COUNT_ERR_RANGE = -1, PCC.COUNT_ERR_RANGE
 
 
 def _read_count(word, device):
@@ -122,12 +122,21 @@ def _read_count(word, device):
         time.sleep(0)
     n = int(word[0])
     if n == COUNT_ERR_RANGE:
-        raise CoordinateRangeError("libpcc_hip: a voxel coordinate is outside the supported range (|c| <= 130000, batch index "
-                                   "<= 1022): the 18-bit fields of the voxel key would alias — translate the cloud towards the "
-                                   "origin or re-voxelise it")
+        raise CoordinateRangeError(f"libpcc_hip: a voxel coordinate is outside the supported range (|c| <= {PCC.COORD_LIMIT}, batch "
+                                   f"index <= {PCC.BATCH_LIMIT}): the 18-bit fields of the voxel key would alias — translate the cloud "
+                                   "towards the origin or re-voxelise it")
     if n < 0:
         raise RuntimeError("libpcc_hip: the row count was never written (kernel failure?)")
     return n
+
+
+def _set_buffers(m, dev):
+    """what a coordinate-set construction over m candidates builds in: the hashed-voxel table of the output set and the scan's
+    scratch -> (keys, vals, cap, scratch)"""
+    L = _lib.lib()
+    cap = L.pcc_hash_capacity(m)
+    return (torch.empty(cap, dtype=torch.int64, device=dev), torch.empty(cap, dtype=torch.int32, device=dev), cap,
+            torch.empty(L.pcc_scan_scratch_elems(m), dtype=torch.int32, device=dev))
 
 
 class PairCount:
@@ -241,17 +250,13 @@ class CoordMap:
 
     # -- derived coordinate sets -------------------------------------------------------------
     def _unique(self, fn_name, m, *args):
-        L = _lib.lib()
-        cap = L.pcc_hash_capacity(m)
         dev = self.device
-        keys = torch.empty(cap, dtype=torch.int64, device=dev)
-        vals = torch.empty(cap, dtype=torch.int32, device=dev)
-        scratch = torch.empty(L.pcc_scan_scratch_elems(m), dtype=torch.int32, device=dev)
+        keys, vals, cap, scratch = _set_buffers(m, dev)
         out = torch.empty((max(m, 1), 4), dtype=torch.int32, device=dev)
         count, word = _host_count()
         ev = _cp_begin()
-        check(getattr(L, fn_name)(ptr(self.coords), self.n, *args, ptr(keys), ptr(vals), cap, ptr(scratch),
-                                  ptr(out), ptr(count), _lib.stream()))
+        check(getattr(_lib.lib(), fn_name)(ptr(self.coords), self.n, *args, ptr(keys), ptr(vals), cap, ptr(scratch),
+                                           ptr(out), ptr(count), _lib.stream()))
         n_out = _read_count(word, dev)      # the one host sync of a coordinate-set construction
         # table cleared, 16 B per source row, 12 B per candidate (key claim + flag), 16 B + 12 B per unique row written
         _cp_end(ev, "unique_" + fn_name[4:], m, 12 * cap + 16 * self.n + 12 * m + 28 * n_out)

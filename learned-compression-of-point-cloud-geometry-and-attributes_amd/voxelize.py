@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
-from .sparse import CoordinateRangeError, _host_count, _read_count, _require_cuda
+from .sparse import CoordinateRangeError, _host_count, _read_count, _require_cuda, _set_buffers
 
 Voxelized = namedtuple("Voxelized", ["coords", "features", "counts", "inverse", "first", "sums"])
 Voxelized.__doc__ = """coords int32 [M,4] (batch, cell x, y, z) in order of first appearance; features float32 [M,C] or None;
@@ -29,7 +29,7 @@ sums int64 [M,C] exact Q32 attribute sums (None without attributes)"""
 
 ROUNDINGS = {"floor": 0, "nearest": 1}
 MAX_CHANNELS = 16
-COORD_LIMIT = 130000
+COORD_LIMIT = _lib.PCC.COORD_LIMIT
 Q32 = 4294967296.0
 
 
@@ -83,7 +83,7 @@ def voxelize(points, attributes=None, voxel_size=1.0, origin=(0, 0, 0), rounding
     order of first appearance, never merged across ``batch`` items (int [N], optional).
     ``reduce="mean"``: ``features`` is the exact mean of each voxel's attributes (rounded once to float32);
     ``reduce="first"``: ``attributes[first]``, the first-occurrence-wins rule.  ``sums`` / ``counts`` are returned either way.
-    Raises ValueError naming the cause when a point is not finite or falls beyond cell +-130000, a batch index is out of range
+    Raises ValueError naming the cause when a point is not finite or falls beyond cell +-PCC_COORD_LIMIT (include/pcc_hip.h), a batch index is out of range
     or an attribute is not finite or exceeds 1 in magnitude.  One synchronisation: reading the voxel count."""
     if rounding not in ROUNDINGS:
         raise ValueError(f"rounding {rounding!r}: 'floor' or 'nearest'")
@@ -112,12 +112,8 @@ def voxelize(points, attributes=None, voxel_size=1.0, origin=(0, 0, 0), rounding
         B = _to_device(batch, torch.int32, dev).reshape(-1)
         if B.shape[0] != n:
             raise ValueError(f"batch of {B.shape[0]} entries for {n} points")
-        nbatch = 1023                 # every index the voxel key can hold (PCC_BATCH_LIMIT + 1): no read of the largest one
-    L = _lib.lib()
-    cap = L.pcc_hash_capacity(n)
-    keys = torch.empty(cap, dtype=torch.int64, device=dev)
-    vals = torch.empty(cap, dtype=torch.int32, device=dev)
-    scratch = torch.empty(L.pcc_scan_scratch_elems(n), dtype=torch.int32, device=dev)
+        nbatch = _lib.PCC.BATCH_LIMIT + 1         # every index the voxel key can hold: no read of the largest one
+    keys, vals, cap, scratch = _set_buffers(n, dev)
     m1 = max(n, 1)
     coords = torch.empty((m1, 4), dtype=torch.int32, device=dev)
     first = torch.empty(m1, dtype=torch.int32, device=dev)
@@ -125,9 +121,9 @@ def voxelize(points, attributes=None, voxel_size=1.0, origin=(0, 0, 0), rounding
     sums = torch.empty((m1, max(c, 1)), dtype=torch.int64, device=dev)
     row = torch.empty(m1, dtype=torch.int32, device=dev)
     count, word = _host_count()
-    check(L.pcc_voxelize(ptr(P), ptr(B), n, nbatch, ptr(A) if c else None, c, origin[0], origin[1], origin[2], voxel_size,
-                         ROUNDINGS[rounding], ptr(keys), ptr(vals), cap, ptr(scratch), ptr(coords), ptr(first), ptr(npts), ptr(sums),
-                         ptr(row), ptr(count), _lib.stream()))
+    check(_lib.lib().pcc_voxelize(ptr(P), ptr(B), n, nbatch, ptr(A) if c else None, c, origin[0], origin[1], origin[2], voxel_size,
+                                  ROUNDINGS[rounding], ptr(keys), ptr(vals), cap, ptr(scratch), ptr(coords), ptr(first), ptr(npts),
+                                  ptr(sums), ptr(row), ptr(count), _lib.stream()))
     try:
         m = _read_count(word, dev)
     except CoordinateRangeError:

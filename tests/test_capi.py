@@ -56,6 +56,66 @@ def test_host_entry_points_without_gpu(pcc):
     assert rc < 0 and b"pmf" in L.pcc_last_error()
 
 
+def test_header_parser_on_planted_text():
+    """parse_header on two prototypes that cover every mapped type: a multi-line parameter list, a (void) list, a const char*
+    return; comments and preprocessor lines are dropped, integer PCC_* defines collected"""
+    from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+    from pcc_amd import _lib
+    text = """
+    /* a comment with a prototype in it: int pcc_not_this(int a); */
+    #include <stdint.h>
+    #define PCC_PLANTED 7
+    #define PCC_PLANTED_NEG (-5)   /* trailing comment */
+    #define PCC_NOT_AN_INT 1.5f
+    extern "C" {
+    const char* pcc_planted_name(void);
+    int64_t pcc_planted(int dev, int32_t a, int64_t n,
+                        float half, char* out, const char *name,
+                        const uint64_t* keys, double * normals,
+                        void* stream);
+    }
+    """
+    protos, consts = _lib.parse_header(text)
+    assert protos == {
+        "pcc_planted_name": (c_char_p, []),
+        "pcc_planted": (c_int64, [("dev", c_int), ("a", c_int32), ("n", c_int64), ("half", c_float), ("out", c_char_p),
+                                  ("name", c_char_p), ("keys", c_void_p), ("normals", c_void_p), ("stream", c_void_p)]),
+    }
+    assert consts == {"PLANTED": 7, "PLANTED_NEG": -5}
+
+
+def test_header_parser_never_guesses():
+    from pcc_amd import _lib
+    for bad in ("int pcc_planted(const float* x, size_t n);", "size_t pcc_planted(void);", "int pcc_planted(float** rows);",
+                "int pcc_planted(int32_t);", "struct pcc_thing { int a };"):
+        with pytest.raises(ValueError):
+            _lib.parse_header(bad)
+
+
+def test_wrong_argument_count_raises(pcc):
+    """a surplus or a missing argument is a TypeError before the call (host-only entry points: nothing is launched)"""
+    L = pcc.lib()
+    buf = ctypes.create_string_buffer(128)
+    with pytest.raises(TypeError):
+        L.pcc_hash_capacity(1000, 0)
+    with pytest.raises(TypeError):
+        L.pcc_conv_kernel_name(0, 1000, 128, 128, 1000, 27, 1, buf, 128, 0)
+    with pytest.raises(TypeError):
+        L.pcc_hash_capacity()
+    assert L.pcc_hash_capacity(1000) == 2048
+    assert L.pcc_conv_kernel_name(0, 1000, 128, 128, 1000, 27, 1, buf, 128) == 0 and buf.value == b"conv_small_kernel<4, 3>"
+
+
+def test_constants_come_from_the_header(pcc):
+    import importlib
+    from pcc_amd import _lib, augment, render, sparse
+    voxelize = importlib.import_module("pcc_amd.voxelize")          # (the package exports the function under the module's name)
+    P = _lib.PCC
+    assert (P.OK, P.COORD_LIMIT, P.BATCH_LIMIT, P.COUNT_ERR_RANGE, P.ERR_UNSUPPORTED, P.ACT_LEAKY_RELU) == (0, 130000, 1022, -2, -3, 2)
+    assert (sparse.ACT_NONE, sparse.ACT_RELU, sparse.ACT_LRELU, sparse.COUNT_ERR_RANGE) == (0, 1, 2, -2)
+    assert augment.BATCH_SLOTS == 1023 and render.COORD_LIMIT == 130000 and voxelize.COORD_LIMIT == 130000
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "learned-compression-of-point-cloud-geometry-and-attributes_amd")
     for dirpath, _, files in os.walk(pkg):
