@@ -203,6 +203,7 @@ struct Rotation {
     const float* rot;        // [nbatch, 9] row-major
     int nbatch;
     float half;
+    static constexpr int shift = 0;      // the output set has tensor stride 1
     static constexpr int REJECT = 1 << 30;
     __device__ __forceinline__ int grid(float v) const {
         const float r = rintf(v);

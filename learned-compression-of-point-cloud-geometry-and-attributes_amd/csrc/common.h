@@ -43,7 +43,7 @@ static inline unsigned blocks_for(int64_t n, int per_block, unsigned cap = 0x7ff
 // of a tensor stride <= 512) inside the field, so a key never wraps onto another voxel's.  The range covers the reference's
 // radix-1e5 keys (model/blocks.py:118, utils.py:170: coordinates 0 .. 99,999) and as much again on the negative side (rounds
 // 1-3 had 16-bit fields: |coord| <= 32,000); a coordinate outside it is an ERROR reported with the row count of the next
-// coordinate-set construction (coords.hip: unique_insert -> COUNT_ERR_RANGE), never an aliased key.
+// coordinate-set construction (first_rows.h: first_rows_insert_kernel -> COUNT_ERR_RANGE), never an aliased key.
 constexpr uint64_t KEY_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 constexpr int KEY_FIELD_BITS = 18;
 constexpr uint32_t KEY_FIELD_MASK = (1u << KEY_FIELD_BITS) - 1u;
@@ -107,7 +107,7 @@ __host__ __device__ __forceinline__ int grid_shift_of(int tensor_stride) {      
 
 // Probe the table.  Returns row id or -1.  A key's lane (every 8th slot from its first one) is searched first; only if that
 // whole lane holds other keys — which needs more than a quarter of a set's voxels in one lane: adversarial input — the
-// search goes on slot by slot from the first slot, exactly as table_claim (coords.hip) placed the key.  Lanes only ever
+// search goes on slot by slot from the first slot, exactly as table_claim (below) placed the key.  Lanes only ever
 // fill, so "the lane is full" reads the same for the insert and for every later lookup.
 __device__ __forceinline__ int table_find(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals,
                                           uint64_t mask, int shift, uint64_t key) {
@@ -126,6 +126,35 @@ __device__ __forceinline__ int table_find(const uint64_t* __restrict__ keys, con
         if (k == KEY_EMPTY) return -1;
     }
     return -1;
+}
+
+// Claim (or find) the slot of `key`; returns the slot index.  The mirror image of table_find, slot for slot — a change to the
+// probing rule of one is a change to the other, or lookups miss.  The key's lane first (every 8th slot); a lane that is full of
+// other keys — more than cap / 8 >= a quarter of the candidates in one lane: improbable, not impossible — hands the key
+// to slot-by-slot probing from its first slot.  With cap >= 2 * candidates a free slot exists, so the second loop always
+// returns; mask + 1 is unreachable and callers still guard it.
+__device__ __forceinline__ uint64_t table_claim(uint64_t* keys, uint64_t mask, int shift, uint64_t key) {
+    const uint64_t slot0 = table_slot0(key, mask, shift);
+    uint64_t slot = slot0;
+    for (uint64_t probe = 0; probe <= mask; probe += TABLE_PROBE_STEP) {
+        uint64_t cur = keys[slot];
+        if (cur == KEY_EMPTY) {
+            cur = (uint64_t)atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)KEY_EMPTY, (unsigned long long)key);
+            if (cur == KEY_EMPTY) return slot;
+        }
+        if (cur == key) return slot;
+        slot = (slot + TABLE_PROBE_STEP) & mask;
+    }
+    for (uint64_t probe = 1; probe <= mask; ++probe) {
+        slot = (slot0 + probe) & mask;
+        uint64_t cur = keys[slot];
+        if (cur == KEY_EMPTY) {
+            cur = (uint64_t)atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)KEY_EMPTY, (unsigned long long)key);
+            if (cur == KEY_EMPTY) return slot;
+        }
+        if (cur == key) return slot;
+    }
+    return mask + 1;
 }
 
 // Kernel offset of index k for kernel size ks (x fastest; ks=3 centred, ks=2 un-centred).

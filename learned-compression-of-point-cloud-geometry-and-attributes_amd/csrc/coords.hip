@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "first_rows.h"
 #include "sort.h"
 
 namespace pcc {
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_block_sums(const int32_t* __r
     if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
 }
 
-// `err` (optional): a device word the producers of the flags set when the set cannot be built (unique_insert: a
+// `err` (optional): a device word the producers of the flags set when the set cannot be built (first_rows_insert_kernel: a
 // coordinate outside the key range); the count that goes to the host is then COUNT_ERR_RANGE instead of a row count,
 // so the error travels with the one value the host reads anyway.
 __global__ __launch_bounds__(SCAN_BLOCK) void scan_of_block_sums(int32_t* __restrict__ block_sums, int64_t nb,
@@ -139,78 +140,36 @@ static int exclusive_scan(const int32_t* flags, int64_t m, int32_t* pos, int32_t
 }
 
 // ---------------------------------------------------------------------------------------------
-// hash table
+// coordinate sets: the candidate generators of first_rows.h's builder (the table's claim / find pair is common.h's)
 // ---------------------------------------------------------------------------------------------
-__global__ void table_clear(uint64_t* __restrict__ keys, int32_t* __restrict__ vals, int64_t cap, int32_t* __restrict__ err) {
-    if (err && blockIdx.x == 0 && threadIdx.x == 0) *err = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (int64_t)gridDim.x * blockDim.x) {
-        keys[i] = KEY_EMPTY;
-        vals[i] = 0x7fffffff;
-    }
-}
-
-// claim (or find) the slot of `key`; returns slot index.  The key's lane first (every 8th slot); a lane that is full of
-// other keys — more than cap / 8 >= a quarter of the candidates in one lane: improbable, not impossible — hands the key
-// to slot-by-slot probing from its first slot, which table_find mirrors.  With cap >= 2 * candidates a free slot exists,
-// so the second loop always returns; mask + 1 is unreachable and callers still guard it.
-__device__ __forceinline__ uint64_t table_claim(uint64_t* keys, uint64_t mask, int shift, uint64_t key) {
-    const uint64_t slot0 = table_slot0(key, mask, shift);
-    uint64_t slot = slot0;
-    for (uint64_t probe = 0; probe <= mask; probe += TABLE_PROBE_STEP) {
-        uint64_t cur = keys[slot];
-        if (cur == KEY_EMPTY) {
-            cur = (uint64_t)atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)KEY_EMPTY,
-                                      (unsigned long long)key);
-            if (cur == KEY_EMPTY) return slot;
-        }
-        if (cur == key) return slot;
-        slot = (slot + TABLE_PROBE_STEP) & mask;
-    }
-    for (uint64_t probe = 1; probe <= mask; ++probe) {
-        slot = (slot0 + probe) & mask;
-        uint64_t cur = keys[slot];
-        if (cur == KEY_EMPTY) {
-            cur = (uint64_t)atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)KEY_EMPTY,
-                                      (unsigned long long)key);
-            if (cur == KEY_EMPTY) return slot;
-        }
-        if (cur == key) return slot;
-    }
-    return mask + 1;
-}
-
-// Candidate generators ------------------------------------------------------------------------
-struct GenRows {  // candidate i = row i
-    const int32_t* coords;
-    __device__ __forceinline__ bool in_range(int64_t) const { return true; }
-    __device__ __forceinline__ void get(int64_t i, int& b, int& x, int& y, int& z) const {
-        const int4 c = reinterpret_cast<const int4*>(coords)[i];
-        b = c.x; x = c.y; y = c.z; z = c.w;
-    }
-};
+// The source row's own coordinates are covered too: |floor(c / 2ts) 2ts| >= |c| - 2ts + 1 and a child is within ts of its parent,
+// so a source coordinate beyond the limit by more than a stride puts its candidate beyond it as well — and GenStride checks the
+// source row directly (ok), after the candidate's own test.
 struct GenStride {  // candidate i = floor(row i / 2ts) * 2ts
     const int32_t* coords;
-    int s2;  // 2 * ts (power of two in practice, but do a true floor division)
-    __device__ __forceinline__ bool in_range(int64_t i) const {
-        const int4 c = reinterpret_cast<const int4*>(coords)[i];
-        return coord_in_range(c.x, c.y, c.z, c.w);
-    }
+    int s2;     // 2 * ts (power of two in practice, but do a true floor division)
+    int shift;  // of the output set's table: log2(2 * ts)
     __device__ __forceinline__ int fl(int v) const {
         int q = v / s2;
         if ((v % s2) != 0 && v < 0) --q;
         return q * s2;
     }
-    __device__ __forceinline__ void get(int64_t i, int& b, int& x, int& y, int& z) const {
+    __device__ __forceinline__ int4 get(int64_t i) const {
         const int4 c = reinterpret_cast<const int4*>(coords)[i];
-        b = c.x; x = fl(c.y); y = fl(c.z); z = fl(c.w);
+        return make_int4(c.x, fl(c.y), fl(c.z), fl(c.w));
+    }
+    __device__ __forceinline__ bool ok(int64_t i, bool in_range) const {
+        if (!in_range) return false;
+        const int4 c = reinterpret_cast<const int4*>(coords)[i];
+        return coord_in_range(c.x, c.y, c.z, c.w);
     }
 };
 struct GenChildren {  // ks=3: candidate i = (parent i / 27, offset i % 27); ks=2: (offset i / n, parent i % n)
     const int32_t* coords;
     int64_t n;
     int ks, half;
-    __device__ __forceinline__ bool in_range(int64_t) const { return true; }     // a child is within half a stride of its parent
-    __device__ __forceinline__ void get(int64_t i, int& b, int& x, int& y, int& z) const {
+    int shift;  // of the output set's table: log2(ts / 2)
+    __device__ __forceinline__ int4 get(int64_t i) const {
         int64_t p;
         int k;
         if (ks == 3) { p = i / 27; k = (int)(i - p * 27); }
@@ -218,57 +177,13 @@ struct GenChildren {  // ks=3: candidate i = (parent i / 27, offset i % 27); ks=
         const int4 c = reinterpret_cast<const int4*>(coords)[p];
         int dx, dy, dz;
         kernel_offset(ks, k, dx, dy, dz);
-        b = c.x; x = c.y + dx * half; y = c.z + dy * half; z = c.w + dz * half;
+        return make_int4(c.x, c.y + dx * half, c.z + dy * half, c.w + dz * half);
     }
+    __device__ __forceinline__ bool ok(int64_t, bool in_range) const { return in_range; }     // a child is within half a stride of its parent
 };
-
-template <class Gen>
-__global__ __launch_bounds__(256) void unique_insert(Gen gen, int64_t m, uint64_t* __restrict__ keys,
-                                                     int32_t* __restrict__ vals, uint64_t mask, int shift,
-                                                     int32_t* __restrict__ slot_of, int32_t* __restrict__ err) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    int b, x, y, z;
-    gen.get(i, b, x, y, z);
-    // the source row's own coordinates are covered too: |floor(c / 2ts) 2ts| >= |c| - 2ts + 1 and a child is within ts of
-    // its parent, so a source coordinate beyond the limit by more than a stride puts its candidate beyond it as well —
-    // and GenStride / GenChildren check the source row directly (in_range)
-    if (!coord_in_range(b, x, y, z) || !gen.in_range(i)) {
-        *err = 1;
-        slot_of[i] = (int32_t)(mask + 1);
-        return;
-    }
-    const uint64_t slot = table_claim(keys, mask, shift, pack_key(b, x, y, z));
-    slot_of[i] = (int32_t)slot;
-    if (slot <= mask) atomicMin(&vals[slot], (int32_t)i);
-}
-
-__global__ __launch_bounds__(256) void unique_flag(int64_t m, const int32_t* __restrict__ vals, uint32_t mask,
-                                                   const int32_t* __restrict__ slot_of, int32_t* __restrict__ flags) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const uint32_t slot = (uint32_t)slot_of[i];
-    flags[i] = (slot <= mask && vals[slot] == (int32_t)i) ? 1 : 0;       // slot > mask: the candidate was rejected (range error)
-}
-
-// incl = inclusive scan of the winner flags: candidate i won its slot iff the scan steps at i, and its output row
-// is incl[i] - 1.  The winner test reads the scan, never `vals`, so the slot can be rewritten to the row id at once.
-template <class Gen>
-__global__ __launch_bounds__(256) void unique_finalize(Gen gen, int64_t m, int32_t* __restrict__ vals,
-                                                       const int32_t* __restrict__ slot_of,
-                                                       const int32_t* __restrict__ incl,
-                                                       int32_t* __restrict__ out_coords) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const int32_t cur = incl[i], prev = i ? incl[i - 1] : 0;
-    if (cur != prev) {
-        const int32_t row = cur - 1;
-        int b, x, y, z;
-        gen.get(i, b, x, y, z);
-        reinterpret_cast<int4*>(out_coords)[row] = make_int4(b, x, y, z);
-        vals[slot_of[i]] = row;
-    }
-}
+struct NoSink {  // a coordinate set alone: a winner writes its output row and nothing else
+    __device__ __forceinline__ void operator()(int32_t, int64_t) const {}
+};
 
 static int g_small_paths = -1;
 static int small_paths_value() {
@@ -292,7 +207,7 @@ bool small_path_enabled(int bit) { return (small_paths_value() >> bit) & 1; }
 // holds a row id <= its winner's index < any later candidate's index, so a later duplicate still reads "not me".
 constexpr int UNIQUE_SMALL_M = 8192;
 template <class Gen>
-__global__ __launch_bounds__(1024) void unique_small_kernel(Gen gen, int m, uint64_t* keys, int32_t* vals, int64_t cap, int shift,
+__global__ __launch_bounds__(1024) void unique_small_kernel(Gen gen, int m, uint64_t* keys, int32_t* vals, int64_t cap,
                                                             int32_t* __restrict__ slot_of, int32_t* __restrict__ out_coords,
                                                             int64_t* __restrict__ out_count, int32_t* __restrict__ err) {
     __shared__ int err_s, carry_s;
@@ -306,14 +221,13 @@ __global__ __launch_bounds__(1024) void unique_small_kernel(Gen gen, int m, uint
     if (t == 0) { err_s = 0; carry_s = 0; }
     __syncthreads();
     for (int i = t; i < m; i += 1024) {
-        int b, x, y, z;
-        gen.get(i, b, x, y, z);
-        if (!coord_in_range(b, x, y, z) || !gen.in_range(i)) {
+        const int4 c = gen.get(i);
+        if (!gen.ok(i, coord_in_range(c.x, c.y, c.z, c.w))) {
             err_s = 1;
             slot_of[i] = (int32_t)(mask + 1);
             continue;
         }
-        const uint64_t slot = table_claim(keys, mask, shift, pack_key(b, x, y, z));
+        const uint64_t slot = table_claim(keys, mask, gen.shift, pack_key(c.x, c.y, c.z, c.w));
         slot_of[i] = (int32_t)slot;
         if (slot <= mask) atomicMin(&vals[slot], (int32_t)i);
     }
@@ -340,9 +254,7 @@ __global__ __launch_bounds__(1024) void unique_small_kernel(Gen gen, int m, uint
         }
         if (flag) {
             const int32_t row = base + inc - 1;
-            int b, x, y, z;
-            gen.get(i, b, x, y, z);
-            reinterpret_cast<int4*>(out_coords)[row] = make_int4(b, x, y, z);
+            reinterpret_cast<int4*>(out_coords)[row] = gen.get(i);
             vals[slot] = row;
         }
         __syncthreads();
@@ -357,36 +269,21 @@ __global__ __launch_bounds__(1024) void unique_small_kernel(Gen gen, int m, uint
 }
 
 template <class Gen>
-static int unique_coords(Gen gen, int64_t m, uint64_t* keys, int32_t* vals, int64_t cap, int shift, int32_t* scratch,
-                         int32_t* out_coords, int64_t* out_count, hipStream_t st) {
+static int unique_coords(const Gen& gen, int64_t m, uint64_t* keys, int32_t* vals, int64_t cap, int32_t* scratch, int32_t* out_coords,
+                         int64_t* out_count, hipStream_t st) {
     PCC_REQUIRE(cap > 0 && (cap & (cap - 1)) == 0, "hash capacity %lld is not a power of two", (long long)cap);
     PCC_REQUIRE(cap >= 2 * m, "hash capacity %lld too small for %lld candidates", (long long)cap, (long long)m);
     PCC_REQUIRE(m < (1ll << 31) - 1, "too many candidates (%lld)", (long long)m);
     PCC_REQUIRE(cap <= (1ll << 31), "hash capacity %lld exceeds 2^31 slots", (long long)cap);
-    int32_t* slot_of = scratch;
-    int32_t* flags = scratch + (m > 0 ? m : 0);
-    int32_t* block_sums = scratch + 2 * (m > 0 ? m : 0);
-    // the error word lives in the 16 spare ints behind the scan's block sums (pcc_scan_scratch_elems); table_clear zeroes it
-    int32_t* err = block_sums + (m > 0 ? (m + SCAN_TILE - 1) / SCAN_TILE : 0) + 8;
+    if (m < 0) m = 0;      // (an empty set, as ever)
     if (small_path_enabled(2) && m > 0 && m <= UNIQUE_SMALL_M && cap <= 8 * UNIQUE_SMALL_M) {      // PCC_UNIQUE_SMALL=0: never (A/B)
-        hipLaunchKernelGGL(unique_small_kernel<Gen>, dim3(1), dim3(1024), 0, st, gen, (int)m, keys, vals, cap, shift, slot_of, out_coords,
-                           out_count, err);
+        const FirstRowsScratch s(scratch, m);
+        hipLaunchKernelGGL(unique_small_kernel<Gen>, dim3(1), dim3(1024), 0, st, gen, (int)m, keys, vals, cap, s.slot_of, out_coords,
+                           out_count, s.err);
         PCC_LAUNCH_CHECK();
         return PCC_OK;
     }
-    hipLaunchKernelGGL(table_clear, dim3(blocks_for(cap, 256, 4096)), dim3(256), 0, st, keys, vals, cap, err);
-    if (m <= 0) {
-        PCC_CHECK_HIP(hipMemsetAsync(out_count, 0, sizeof(int64_t), st));
-        return PCC_OK;
-    }
-    const unsigned nb = blocks_for(m, 256);
-    hipLaunchKernelGGL(unique_insert<Gen>, dim3(nb), dim3(256), 0, st, gen, m, keys, vals, (uint64_t)(cap - 1), shift, slot_of, err);
-    hipLaunchKernelGGL(unique_flag, dim3(nb), dim3(256), 0, st, m, vals, (uint32_t)(cap - 1), slot_of, flags);
-    int rc = scan_flags(flags, m, flags, block_sums, out_count, 1, st, err);
-    if (rc) return rc;
-    hipLaunchKernelGGL(unique_finalize<Gen>, dim3(nb), dim3(256), 0, st, gen, m, vals, slot_of, flags, out_coords);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    return first_rows_build(gen, NoSink{}, m, keys, vals, cap, scratch, out_coords, out_count, st);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -768,7 +665,7 @@ int pcc_hash_build(const int32_t* coords, int64_t n, uint64_t* keys, int32_t* va
     const int shift = grid_shift_of(tensor_stride);
     PCC_REQUIRE(cap > 0 && (cap & (cap - 1)) == 0 && cap >= 2 * n, "pcc_hash_build: bad capacity %lld for n=%lld",
                 (long long)cap, (long long)n);
-    hipLaunchKernelGGL(table_clear, dim3(blocks_for(cap, 256, 4096)), dim3(256), 0, st, keys, vals, cap, (int32_t*)nullptr);
+    hipLaunchKernelGGL(first_rows_clear_kernel, dim3(blocks_for(cap, 256, 4096)), dim3(256), 0, st, keys, vals, cap, (int32_t*)nullptr);
     if (dup_count) PCC_CHECK_HIP(hipMemsetAsync(dup_count, 0, sizeof(int32_t), st));
     if (n > 0) {
         hipLaunchKernelGGL(build_insert, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, keys, vals,
@@ -795,8 +692,8 @@ int pcc_hash_lookup(const uint64_t* keys, const int32_t* vals, int64_t cap, int3
 int pcc_stride_map(const int32_t* coords, int64_t n, int32_t ts, uint64_t* keys, int32_t* vals, int64_t cap,
                    int32_t* scratch, int32_t* out_coords, int64_t* out_count, void* stream) {
     PCC_REQUIRE(ts >= 1, "pcc_stride_map: tensor stride must be >= 1");
-    GenStride gen{coords, 2 * ts};
-    return unique_coords(gen, n, keys, vals, cap, grid_shift_of(2 * ts), scratch, out_coords, out_count, as_stream(stream));
+    GenStride gen{coords, 2 * ts, grid_shift_of(2 * ts)};
+    return unique_coords(gen, n, keys, vals, cap, scratch, out_coords, out_count, as_stream(stream));
 }
 
 int pcc_children(const int32_t* coords, int64_t n, int32_t ts, int32_t ksize, uint64_t* keys, int32_t* vals,
@@ -804,8 +701,8 @@ int pcc_children(const int32_t* coords, int64_t n, int32_t ts, int32_t ksize, ui
     PCC_REQUIRE(ksize == 2 || ksize == 3, "pcc_children: kernel size must be 2 or 3");
     PCC_REQUIRE(ts >= 2 && (ts % 2) == 0, "pcc_children: tensor stride %d is not even", ts);
     const int K = ksize * ksize * ksize;
-    GenChildren gen{coords, n, ksize, ts / 2};
-    return unique_coords(gen, n * K, keys, vals, cap, grid_shift_of(ts / 2), scratch, out_coords, out_count, as_stream(stream));
+    GenChildren gen{coords, n, ksize, ts / 2, grid_shift_of(ts / 2)};
+    return unique_coords(gen, n * K, keys, vals, cap, scratch, out_coords, out_count, as_stream(stream));
 }
 
 int32_t pcc_small_paths(int32_t mask) {

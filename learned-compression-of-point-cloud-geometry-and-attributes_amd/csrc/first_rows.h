@@ -1,15 +1,17 @@
-// First-row-wins coordinate sets for the operators that live outside coords.hip (the rotation of augment.hip, the voxelisation of
-// voxelize.hip): unique candidate rows in order of first appearance, the lowest candidate index wins.
+// First-row-wins coordinate sets: unique candidate rows in order of first appearance, the lowest candidate index wins.  The one
+// builder of the library: the coordinate manager's stride maps and generative child sets (coords.hip, unique_coords), the rotation
+// (augment.hip) and the voxelisation (voxelize.hip) all go through first_rows_build.
 //
-// The scheme is the coordinate manager's (coords.hip, unique_coords): claim the candidate's slot in the hashed-voxel table, atomicMin
-// the candidate index into the slot's value, flag the winners, scan the flags, and let every winner write its output row and
-// turn its slot's value into the row id — so the result does not depend on thread arrival order and the table indexes the output
-// set on return.  It lives here because coords.hip is part of the kernel-source stamp of the benchmark's committed HBM-traffic
-// profile (bench.py, kernel_source_sha256): operators added beside it must not edit it.  Always the seven-launch form (clear,
-// insert, flag, three scan kernels, finalize); the scan and the count word are coords.hip's scan_flags.
+// The scheme: claim the candidate's slot in the hashed-voxel table (table_claim, common.h), atomicMin the candidate index into the
+// slot's value, flag the winners, scan the flags, and let every winner write its output row and turn its slot's value into the row
+// id — so the result does not depend on thread arrival order and the table indexes the output set on return.  Seven launches
+// (clear, insert, flag, three scan kernels, finalize); the scan and the count word are coords.hip's scan_flags.  (The coordinate
+// manager alone also has a one-workgroup form for small sets, coords.hip unique_small_kernel, over the same generators.)
 //
 // An operator supplies two function objects, passed to the kernels by value:
-//   Gen:  int4 get(int64_t i)  the candidate's (batch, x, y, z); a candidate to reject gets coordinates coord_in_range refuses
+//   Gen:  int shift            log2 of the output set's tensor stride (table_slot0); `static constexpr int shift = 0` for a set of
+//                              stride 1, which folds the shift out of its kernels
+//         int4 get(int64_t i)  the candidate's (batch, x, y, z); a candidate to reject gets coordinates coord_in_range refuses
 //         bool ok(int64_t i, bool in_range)   the whole validity test: in_range (coord_in_range of get(i)) and whatever else the
 //                              operator requires of candidate i, evaluated in that order (nothing is read for one out of range)
 //   Sink: void operator()(int32_t row, int64_t i)   what winner i writes beside its output row
@@ -21,33 +23,6 @@
 
 namespace pcc {
 
-// claim (or find) the slot of `key`: the mirror image of table_find (common.h), slot for slot, for a table of tensor stride 1: the
-// key's lane first (every 8th slot), then slot by slot.  With cap >= 2 * candidates a free slot exists, so the second loop always
-// returns; mask + 1 is unreachable and the callers still guard it.
-__device__ __forceinline__ uint64_t table_claim_slot(uint64_t* keys, uint64_t mask, uint64_t key) {
-    const uint64_t slot0 = table_slot0(key, mask, 0);
-    uint64_t slot = slot0;
-    for (uint64_t probe = 0; probe <= mask; probe += TABLE_PROBE_STEP) {
-        uint64_t cur = keys[slot];
-        if (cur == KEY_EMPTY) {
-            cur = (uint64_t)atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)KEY_EMPTY, (unsigned long long)key);
-            if (cur == KEY_EMPTY) return slot;
-        }
-        if (cur == key) return slot;
-        slot = (slot + TABLE_PROBE_STEP) & mask;
-    }
-    for (uint64_t probe = 1; probe <= mask; ++probe) {
-        slot = (slot0 + probe) & mask;
-        uint64_t cur = keys[slot];
-        if (cur == KEY_EMPTY) {
-            cur = (uint64_t)atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)KEY_EMPTY, (unsigned long long)key);
-            if (cur == KEY_EMPTY) return slot;
-        }
-        if (cur == key) return slot;
-    }
-    return mask + 1;
-}
-
 // scratch as pcc_scan_scratch_elems(n) lays it out: slot per candidate, flags, the scan's block sums, then the error word
 struct FirstRowsScratch {
     int32_t *slot_of, *flags, *block_sums, *err;
@@ -57,7 +32,7 @@ struct FirstRowsScratch {
 
 static __global__ __launch_bounds__(256) void first_rows_clear_kernel(uint64_t* __restrict__ keys, int32_t* __restrict__ vals,
                                                                       int64_t cap, int32_t* __restrict__ err) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *err = 0;
+    if (err && blockIdx.x == 0 && threadIdx.x == 0) *err = 0;      // (null: a table built without a set, pcc_hash_build)
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (int64_t)gridDim.x * blockDim.x) {
         keys[i] = KEY_EMPTY;
         vals[i] = 0x7fffffff;
@@ -76,7 +51,7 @@ __global__ __launch_bounds__(256) void first_rows_insert_kernel(Gen gen, int64_t
         slot_of[i] = (int32_t)(mask + 1);
         return;
     }
-    const uint64_t slot = table_claim_slot(keys, mask, pack_key(c.x, c.y, c.z, c.w));
+    const uint64_t slot = table_claim(keys, mask, gen.shift, pack_key(c.x, c.y, c.z, c.w));
     slot_of[i] = (int32_t)slot;
     if (slot <= mask) atomicMin(&vals[slot], (int32_t)i);
 }
@@ -90,7 +65,8 @@ static __global__ __launch_bounds__(256) void first_rows_flag_kernel(int64_t m, 
     flags[i] = (slot <= mask && vals[slot] == (int32_t)i) ? 1 : 0;       // slot > mask: the candidate was rejected (range error)
 }
 
-// incl = inclusive scan of the winner flags: candidate i won iff the scan steps at i, and its output row is incl[i] - 1
+// incl = inclusive scan of the winner flags: candidate i won its slot iff the scan steps at i, and its output row is incl[i] - 1.
+// The winner test reads the scan, never `vals`, so the slot can be rewritten to the row id at once.
 template <class Gen, class Sink>
 __global__ __launch_bounds__(256) void first_rows_finalize_kernel(Gen gen, Sink sink, int64_t m, int32_t* __restrict__ vals,
                                                                   const int32_t* __restrict__ slot_of,

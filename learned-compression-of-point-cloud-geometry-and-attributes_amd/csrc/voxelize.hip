@@ -27,6 +27,7 @@ struct Voxelizer {
     int nbatch;
     float ox, oy, oz, voxel;
     int rounding;             // 0 floorf, 1 rintf (ties to even)
+    static constexpr int shift = 0;      // the output set has tensor stride 1
     static constexpr int REJECT = 1 << 30;
     __device__ __forceinline__ int cell(float p, float o) const {
         const float g = (p - o) / voxel;

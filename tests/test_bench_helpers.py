@@ -64,6 +64,17 @@ def test_kernel_source_hash_covers_the_coordinate_side_too():
     assert {"conv.hip", "common.h", "coords.hip", "sort.hip", "select.hip", "sort.h", "sort_small.h"} <= set(bench.KERNEL_SOURCES)
 
 
+def test_hbm_operator_table_names_the_first_row_kernels():
+    """bench.py's roofline_hbm groups kernels by tools/pmc_hbm_ops.py's table: the coordinate sets' kernels are first_rows.h's"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from pmc_hbm_ops import operator_of
+    assert operator_of("void pcc::first_rows_insert_kernel<pcc::GenChildren>(pcc::GenChildren, long, unsigned long*, int*, unsigned long, int*, int*)") == "unique_children"
+    assert operator_of("void pcc::first_rows_finalize_kernel<pcc::GenStride, pcc::NoSink>(pcc::GenStride, pcc::NoSink, long, int*, int const*, int const*, int*)") == "unique_stride_map"
+    shared = operator_of("pcc::scan_apply(int const*, long, int const*, int*, int)")
+    assert shared == operator_of("pcc::first_rows_flag_kernel(long, int const*, unsigned int, int const*, int*)") \
+        == operator_of("pcc::first_rows_clear_kernel(unsigned long*, int*, long, int*)") and shared.startswith("unique / prune")
+
+
 def test_visible_gpu_count_reads_the_environment_not_the_runtime(monkeypatch):
     """the launcher of `--gpus N` counts devices without touching the HIP runtime: the visible-devices variables
     decide when set; this container has no GPU nodes in /sys/class/kfd"""

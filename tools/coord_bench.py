@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the coordinate-side kernels on config-2-sized sets (HIP events, median of 5):
-generative children of a 850 k-row stride-2 shell (~5 M candidates), the transposed parent->candidate kernel map,
+the stride map and the generative children of a 850 k-row stride-2 shell (~5 M candidates), the transposed parent->candidate kernel map,
 the candidate->candidate kernel map, and the MFMA execution order (radix sort + permuted table) of both.
 
 """
@@ -34,6 +34,8 @@ def fresh():
     return pcc_amd.CoordMap(par_d, 2, nbatch=1)
 
 
+t, down = timed(lambda: fresh().down())
+print(f"stride map (unique) of {par.shape[0]} rows -> {down.n} rows: {t:.3f} ms")
 t, cand = timed(lambda: fresh().up(3))
 print(f"children (unique) of {par.shape[0]} parents -> {cand.n} candidates: {t:.3f} ms")
 p = fresh()

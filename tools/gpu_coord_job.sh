@@ -28,6 +28,6 @@ for d in sorted(glob.glob("gpurun_out/${TAG}_coord_pmc_*/")):
             k = (r["Kernel_Name"].split("(")[0][-60:], r["Counter_Name"])
             agg[k][0] += 1; agg[k][1] += float(r["Counter_Value"])
         for (kn, cn), (n, v) in sorted(agg.items()):
-            if any(s in kn for s in ("kernel_map27", "radix_scatter", "radix_count", "unique_insert", "group_masks", "mask_bit")):
+            if any(s in kn for s in ("kernel_map27", "radix_scatter", "radix_count", "first_rows_insert_kernel", "group_masks", "mask_bit")):
                 print(f"{kn:62s} {cn:24s} launches {n:4d}  mean {v / n:16.1f}")
 PY

@@ -25,9 +25,9 @@ OPERATOR_OF = [            # first match wins; names as pcc_amd/sparse.py logs t
     (r"small_map_kernel", "small_map+order"),
     (r"mask_bit_counts_kernel|order_keys32|order_keys64|group_masks_kernel|order_small_kernel|radix_\w+_kernel<unsigned int|radix_rowscan", "execution_order"),
     (r"coords_to_keys|radix_\w+_kernel<unsigned long|radix_sort_small_kernel<unsigned long", "canonical_sort"),
-    (r"unique_insert<pcc::GenChildren|unique_finalize<pcc::GenChildren", "unique_children"),
-    (r"unique_insert<pcc::GenStride|unique_finalize<pcc::GenStride", "unique_stride_map"),
-    (r"unique_flag|unique_small_kernel|scan_block_sums|scan_of_block_sums|scan_apply|table_clear", "unique / prune (shared: flags, scans, table clear)"),
+    (r"first_rows_(insert|finalize)_kernel<pcc::GenChildren", "unique_children"),
+    (r"first_rows_(insert|finalize)_kernel<pcc::GenStride", "unique_stride_map"),
+    (r"first_rows_flag_kernel|unique_small_kernel|scan_block_sums|scan_of_block_sums|scan_apply|first_rows_clear_kernel", "unique / prune (shared: flags, scans, table clear)"),
     (r"build_insert|build_count_dups", "hash_build"),
     (r"lookup_kernel", "hash_lookup"),
     (r"topk_", "top_k"),
