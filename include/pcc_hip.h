@@ -644,6 +644,48 @@ int pcc_rans_lanes_encode(const int32_t* symbols, const int32_t* indexes, int64_
 int pcc_rans_lanes_decode(const uint8_t* data_host, const uint8_t* data, int64_t nbytes, const int32_t* indexes,
                           int64_t n, const void* tables, int32_t* out_symbols, int32_t* status, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * RAHT, the region-adaptive hierarchical transform (de Queiroz & Chou 2016): the attribute
+ * transform of the octree + RAHT anchor codec (DESIGN.md "Anchor codec").  csrc/raht.hip.
+ *
+ * Rows are the n distinct voxels of one cloud in ascending Morton order of (c - origin) over
+ * `depth` bits per axis: key bit 3b+2 is x's bit b, 3b+1 y's, 3b z's (the child index
+ * (x<<2)|(y<<1)|z of pcc_octree_occupancy; pcc_octree_expand's output is in row order).
+ * There are 3*depth steps, s = 0 (the finest key bit) upward.  At step s two nodes whose keys
+ * agree in key >> (s+1) merge: the left one (bit s = 0) has w0 points and value a0, the right
+ * one w1 and a1; per channel, in float64, each operation rounded separately:
+ *     low  = (sqrt(w0)*a0 + sqrt(w1)*a1) / sqrt(w0+w1)
+ *     high = (sqrt(w0)*a1 - sqrt(w1)*a0) / sqrt(w0+w1)
+ * `low` stays in the first row of the left node, `high` goes to the first row of the right
+ * node and is final; a node without a sibling passes up unchanged.  Afterwards row 0 holds
+ * the DC and every other row one high-pass coefficient.  The inverse runs the steps top first:
+ *     a0 = (sqrt(w0)*low - sqrt(w1)*high) / sqrt(w0+w1)
+ *     a1 = (sqrt(w1)*low + sqrt(w0)*high) / sqrt(w0+w1)
+ * No atomics touch the values: the result is bitwise reproducible.
+ * ------------------------------------------------------------------------------------- */
+int64_t pcc_raht_scratch_bytes(int64_t n);
+/* The plan of coords [n,4] int32 (batch column ignored), n >= 1, 0 <= depth <= 17; origin is
+ * a HOST int32[3], everything else DEVICE.  Outputs, int32: perm[n] = input row of every
+ * Morton row; per row i > 0 step[i] = index of the highest set bit of key[i] ^ key[i-1] (the
+ * one step at which row i receives its coefficient), left[i] = the first row whose
+ * key >> (step+1) equals row i's (its partner), w0[i] = i - left[i], w1[i] = the number of rows
+ * from i on that share row i's key >> step; row 0 has step -1, left 0, w0 = w1 = 0.
+ * step_rows[n] = the rows in order of (step, row), the rows without a step last;
+ * step_offsets[3*depth+1]: step s owns step_rows[step_offsets[s] .. step_offsets[s+1]).
+ * status[0] = rows outside the grid [origin, origin + 2^depth)^3 (their key is 0), status[1] =
+ * rows whose voxel an earlier row holds (they get step -1 and left = their own row); when
+ * either is non-zero the plan describes no transform.  scratch: pcc_raht_scratch_bytes(n). */
+int pcc_raht_plan(const int32_t* coords, int64_t n, const int32_t* origin, int32_t depth, int32_t* perm,
+                  int32_t* step, int32_t* left, int32_t* w0, int32_t* w1, int32_t* step_rows,
+                  int32_t* step_offsets, int32_t* status, void* scratch, int64_t scratch_bytes, void* stream);
+/* values [n,c] float64 (DEVICE, rows in Morton order, 1 <= c <= 16) transformed in place: one
+ * launch per non-empty step, and one for the run of steps at the top that have at most 256
+ * rows each (the same operations in the same order); inverse = 0 forward, 1 inverse.  step_offsets_host: a HOST copy of
+ * the plan's step_offsets (checked: ascending from 0, at most n). */
+int pcc_raht_transform(double* values, int64_t n, int32_t c, const int32_t* left, const int32_t* w0,
+                       const int32_t* w1, const int32_t* step_rows, const int32_t* step_offsets_host,
+                       int32_t depth, int32_t inverse, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,8 @@ NO_SCRATCH = {
     # (scratch) copy of a point's channels would sit in front of every atomic of the accumulation pass
     "voxelize": ("first_rows_clear_kernel", "first_rows_insert_kernel", "first_rows_flag_kernel", "first_rows_finalize_kernel",
                  "voxelize_accumulate_kernel"),
+    # RAHT (csrc/raht.hip): a step is two gathered float64 rows in, two out; a spill would sit between the gather and the store
+    "raht": ("raht_plan_kernel", "raht_step_kernel", "raht_fold_kernel"),
 }
 
 

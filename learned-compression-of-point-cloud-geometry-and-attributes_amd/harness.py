@@ -110,6 +110,46 @@ def evaluate_frame(experiment, model, data, q_a, q_g, device, base_path, resolut
     return row
 
 
+def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, colorspace="yuv"):
+    """one row of the sweep table for the octree + RAHT anchor codec (anchor.py) at quantisation step ``qstep``: the keys of
+    ``evaluate_frame``'s row without the quality-map pair, plus ``qstep`` and ``codec``.  ``bpp`` counts the whole PCA1 stream;
+    the geometry is lossless, so ``sym_p2p_psnr`` is inf and ``n_decoded`` equals ``n_source``.  ``downsample`` and
+    ``resolution`` mean what they mean in ``evaluate_frame``: the anchor's lossy-geometry rate points are coarser grids."""
+    from . import anchor
+    n_input = None
+    if downsample is not None:
+        if not float(downsample) >= 1.0:
+            raise ValueError(f"downsample {downsample}: a factor of at least 1")
+        n_input = int(data["src"]["points"].shape[1])
+        data, _, _ = downsample_frame(data, downsample, device)
+        resolution = max(1, int(round((resolution + 1) / float(downsample))) - 1)
+    points = data["src"]["points"].to(device, dtype=torch.float)
+    colors = data["src"]["colors"].to(device, dtype=torch.float)
+    src = torch.cat([points, colors], dim=2)[0]
+
+    torch.cuda.synchronize()
+    t0 = time.time()
+    stream = anchor.compress(src, qstep, colorspace=colorspace)
+    torch.cuda.synchronize()
+    t_c = time.time() - t0
+
+    torch.cuda.synchronize()
+    t0 = time.time()
+    rec = anchor.decompress(stream, device)
+    torch.cuda.synchronize()
+    t_d = time.time() - t0
+
+    metric = PointCloudMetric(src, rec, resolution=resolution, device=device)
+    res, _ = metric.compute_pointcloud_metrics(drop_duplicates=True)
+    row = {"codec": "octree+raht", "qstep": float(qstep), "bpp": len(stream) * 8 / src.shape[0], "t_compress": t_c, "t_decompress": t_d,
+           "n_source": int(src.shape[0]), "n_decoded": int(rec.shape[0]),
+           "sym_p2p_psnr": res["sym_psnr_mse"], "sym_y_psnr": res["sym_y_psnr"], "sym_u_psnr": res["sym_u_psnr"],
+           "sym_v_psnr": res["sym_v_psnr"]}
+    if downsample is not None:
+        row["downsample"], row["n_input"] = float(downsample), n_input
+    return row
+
+
 def _extent(points, axis):
     c = points[:, axis]
     return float(c.min()), float(c.max())

@@ -6,17 +6,19 @@ Seeded random weights in their q-RESPONSIVE variant (synthetic.FILM_GAIN_Q_RESPO
 follows the quality map; PCC_SWEEP_FILM_GAIN overrides): the rate axis is a real sweep, the distortion axis is that of random
 weights — not codec quality.
 
-usage: rd_sweep.py [--d2 R] [--downsample F] [out.json] [weights.pt]
+usage: rd_sweep.py [--d2 R] [--downsample F] [--anchor] [out.json] [weights.pt]
   --d2 R: add the point-to-plane PSNR, normals over R voxels
   --downsample F: code every frame on a grid F times coarser (pcc_amd.voxelize: exact mean colours; the reference's "QA" factors
-                  are 1, 2, 4, 8), metrics against the down-sampled source"""
+                  are 1, 2, 4, 8), metrics against the down-sampled source
+  --anchor: also code every frame with the octree + RAHT anchor codec (pcc_amd.anchor) at qstep = {2, 4, 8, 16, 32, 64} / 255 and
+            report the model's BD-rate and BD-PSNR (Y) against the anchor's curve of the same frame"""
 import json, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch
 import pcc_amd
 from pcc_amd import synthetic as syn
-from pcc_amd.harness import evaluate_frame
+from pcc_amd.harness import evaluate_anchor, evaluate_frame
 from pcc_amd.metrics import Bjontegaard_Delta, Bjontegaard_Model
 
 dev = "cuda:0"
@@ -30,6 +32,10 @@ if "--downsample" in sys.argv:
     at = sys.argv.index("--downsample")
     downsample = float(sys.argv[at + 1])
     del sys.argv[at:at + 2]
+with_anchor = "--anchor" in sys.argv
+if with_anchor:
+    sys.argv.remove("--anchor")
+ANCHOR_QSTEPS = [q / 255 for q in (2, 4, 8, 16, 32, 64)]
 FRAMES = {"redandblack~": 247.0, "loot~": 255.0, "longdress~": 261.5, "soldier~": 294.5}   # shell radii -> ~0.76 / 0.81 / 0.86 / 1.09 M
 QS = [(0.05, 0.1), (0.1, 0.2), (0.2, 0.4), (0.4, 0.8)]
 film_gain = float(os.environ.get("PCC_SWEEP_FILM_GAIN", syn.FILM_GAIN_Q_RESPONSIVE))
@@ -37,7 +43,7 @@ model = syn.make_model(seed=0, device=dev, film_gain=film_gain)
 if len(sys.argv) > 2:
     model.load_state_dict(torch.load(sys.argv[2], map_location=dev))
 model.update()
-rows = []
+rows, anchor_rows = [], []
 with tempfile.TemporaryDirectory() as td:
     for name, radius in FRAMES.items():
         pts = syn.sphere_shell(grid=1024, radius=radius, half_width=0.5, noise=0.02)
@@ -50,6 +56,13 @@ with tempfile.TemporaryDirectory() as td:
             print(f"{name:13s} N={row['n_source']:8d} q=({q_g},{q_a}) bpp {row['bpp']:.3f} D1 {row['sym_p2p_psnr']:.2f} Y {row['sym_y_psnr']:.2f} "
                   + (f"D2 {row['sym_d2_psnr']:.2f} " if d2_radius is not None else "") +
                   f"t_enc {row['t_compress']*1e3:.0f} ms t_dec {row['t_decompress']*1e3:.0f} ms (row {time.time()-t0:.1f} s)", flush=True)
+        for qstep in (ANCHOR_QSTEPS if with_anchor else ()):
+            t0 = time.time()
+            row = evaluate_anchor(data, qstep, dev, downsample=downsample)
+            row["frame"] = name
+            anchor_rows.append(row)
+            print(f"{name:13s} N={row['n_source']:8d} anchor qstep {qstep * 255:.0f}/255 bpp {row['bpp']:.3f} Y {row['sym_y_psnr']:.2f} "
+                  f"t_enc {row['t_compress']*1e3:.0f} ms t_dec {row['t_decompress']*1e3:.0f} ms (row {time.time()-t0:.1f} s)", flush=True)
 bd = {}
 names = list(FRAMES)
 ref = [r for r in rows if r["frame"] == names[0]]
@@ -61,9 +74,30 @@ for nm in names[1:]:
         bd[nm] = {"bd_psnr_y_vs_" + names[0]: float(Bjontegaard_Delta().compute_BD_PSNR(m1, m2))}
     except Exception as e:      # degenerate curves (seeded weights) must not lose the table
         bd[nm] = {"error": repr(e)}
+for nm in (names if with_anchor else ()):
+    cur, anc = [r for r in rows if r["frame"] == nm], [r for r in anchor_rows if r["frame"] == nm]
+    entry = bd.setdefault(nm, {})
+    try:                        # model1 = the anchor: the deltas are the model's against it (negative BD-rate = the model needs fewer bits)
+        m1 = Bjontegaard_Model([r["bpp"] for r in anc], [r["sym_y_psnr"] for r in anc])
+        m2 = Bjontegaard_Model([r["bpp"] for r in cur], [r["sym_y_psnr"] for r in cur])
+        # (a delta is a mean over the interval both curves cover; without one there is nothing to average)
+        if max(m1.psnr_values.min(), m2.psnr_values.min()) < min(m1.psnr_values.max(), m2.psnr_values.max()):
+            entry["bd_rate_y_vs_anchor"] = float(Bjontegaard_Delta().compute_BD_Rate(m1, m2))
+        else:
+            entry["bd_rate_y_vs_anchor"] = None
+            entry["error_vs_anchor"] = "the Y-PSNR ranges of the model's and the anchor's curve do not overlap: no BD-rate"
+        if max(m1.bitrates.min(), m2.bitrates.min()) < min(m1.bitrates.max(), m2.bitrates.max()):
+            entry["bd_psnr_y_vs_anchor"] = float(Bjontegaard_Delta().compute_BD_PSNR(m1, m2))
+        else:
+            entry["bd_psnr_y_vs_anchor"] = None
+            entry["error_vs_anchor"] = entry.get("error_vs_anchor", "") + " the rate ranges do not overlap: no BD-PSNR"
+    except Exception as e:      # curves that do not overlap, or degenerate fits
+        entry["error_vs_anchor"] = repr(e)
 out = {"rows": rows, "bjontegaard": bd,
        "note": ("weights from " + os.path.basename(sys.argv[2]) if len(sys.argv) > 2 else "seeded random weights") +
                f" (FiLM-head gain {film_gain}); synthetic shells sized like the 8iVFB frames",
+       **({"anchor_rows": anchor_rows, "anchor": "octree + RAHT (pcc_amd.anchor): lossless PCO1 geometry, BT.709 YUV attributes, "
+                                                  "qstep = {2, 4, 8, 16, 32, 64} / 255"} if with_anchor else {}),
        "rate_axis_monotone_in_q": {nm: [r["bpp"] for r in rows if r["frame"] == nm] == sorted(r["bpp"] for r in rows if r["frame"] == nm)
                                    for nm in names}}
 path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "rd_sweep.json")
