@@ -165,6 +165,13 @@ __device__ __forceinline__ void kernel_offset(int ks, int k, int& dx, int& dy, i
     dx = ix - c; dy = iy - c; dz = iz - c;
 }
 
+// ---- the 32 x 32 MFMA accumulator (v_mfma_f32_32x32x2_f32, v_mfma_f32_32x32x16_bf16): lane (r = lane & 31, h = lane >> 5)
+// holds in register `reg` the element D[mfma32_row(reg) + 4 h][r] of the tile.  The convolution epilogue (conv.hip) and the
+// partial-image stores of the weight gradient (conv_bwd.hip) walk their accumulators through this one map.
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ constexpr int mfma32_row(int reg) { return (reg & 3) + 8 * (reg >> 2); }
+
 // One-workgroup forms of the small per-map chains (bit 0: execution order <= 16,384 rows, bit 1: top-k <= 32,768 rows, bit 2:
 // coordinate sets <= 8,192 candidates): on unless PCC_ORDER_SMALL=0 / PCC_TOPK_SMALL=0 / PCC_UNIQUE_SMALL=0, or switched at run
 // time through pcc_small_paths (coords.hip; A/B measurements in one process).

@@ -24,7 +24,6 @@ namespace pcc {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct ConvArgs {
@@ -40,13 +39,29 @@ struct ConvArgs {
     const float* residual;  // [n_out, cout] or null
     int64_t n_in, n_out;
     int cin, cout, coutp, K, act;
-    int bf16;    // buffer kernel: fin / wp hold bf16 (pcc_conv_fwd_bf16); accumulation and output stay fp32
 };
 
 __device__ __forceinline__ float apply_act(float v, int act) {
     if (act == PCC_ACT_RELU) return v > 0.0f ? v : 0.0f;
     if (act == PCC_ACT_LEAKY_RELU) return v > 0.0f ? v : 0.01f * v;
     return v;
+}
+
+// The output epilogue of every forward kernel: out[row, col] = act(film(acc + bias)) + residual, `bcol` = conv_bias of the
+// column (loaded once per column by the caller).  The roundings happen in this order in every kernel — bias add, FiLM
+// multiply, FiLM add (separate operations: -ffp-contract=off), activation, residual add — which is one half of what makes
+// every kernel and tile plan_conv can pick give the same bits (the other half is the accumulation order).
+__device__ __forceinline__ float conv_bias(const ConvArgs& a, int col) { return a.bias ? a.bias[col] : 0.0f; }
+
+__device__ __forceinline__ void conv_store(const ConvArgs& a, int64_t row, int col, float acc, float bcol) {
+    float v = acc + bcol;
+    if (a.film) {
+        const float* fr = a.film + row * (2 * (int64_t)a.cout);
+        v = v * fr[col] + fr[a.cout + col];
+    }
+    v = apply_act(v, a.act);
+    if (a.residual) v += a.residual[row * a.cout + col];
+    a.fout[row * a.cout + col] = v;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -134,6 +149,141 @@ __device__ float g_zero_line[256] = {0.0f};   // cin <= 256: the per-step channe
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
+// ---- the pieces conv_mfma_kernel and conv_mfma_buf_kernel are both built from (BM x BN output tile, four waves, each
+// MT x NT MFMA tiles of 32 x 32; the two kernels differ in how operands reach LDS and in the shape of the main loop) ----
+
+// Which kernel offsets are live for the tile at row0 (returned) and for each of this wave's 32-row MFMA tiles (mmask[m],
+// rows row0 + wrow + 32 m ..).  All of them wave-uniform by construction, and made provably so (readfirstlane: SGPRs).
+template <int BM, int MT>
+__device__ __forceinline__ uint32_t conv_live_offsets(const ConvArgs& a, int64_t row0, int wrow, uint32_t (&mmask)[MT]) {
+    const uint32_t all = (a.K >= 32) ? 0xffffffffu : ((1u << a.K) - 1u);
+    uint32_t tmask;
+    if (a.gmask) {
+        const int64_t g0 = row0 >> 5;
+        const int64_t ng = (a.n_out + 31) >> 5;
+        tmask = 0u;
+#pragma unroll
+        for (int g = 0; g < BM / 32; ++g) tmask |= (g0 + g < ng) ? (a.gmask[g0 + g] & all) : 0u;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const int64_t g = g0 + (wrow >> 5) + m;
+            const uint32_t v = (g < ng) ? (a.gmask[g] & all) : 0u;
+            mmask[m] = __builtin_amdgcn_readfirstlane(v);
+        }
+    } else {
+        tmask = all;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) mmask[m] = all;
+    }
+    return __builtin_amdgcn_readfirstlane(tmask);
+}
+
+// Byte offset, inside an A image (unpadded 128-B rows, 16-B slots XOR-swizzled by (row >> 1) & 7), of the fragment lane
+// (r, h) reads for sub-block kk: the 16-B chunk 2 kk + h of row `row` (= wave row + 32 m + r; the swizzle has period 16 rows,
+// so m moves the address by whole rows only).  Physical slot = chunk ^ sw, i.e. bit 0 -> h ^ (sw & 1), bits 1-2 -> kk ^ (sw >> 1).
+__device__ __forceinline__ uint32_t a_frag_offset(int row, int h, int kk) {
+    const int sw = (row >> 1) & 7;
+    return (uint32_t)((row * A_LD_DMA + (((kk ^ (sw >> 1)) << 1) | (h ^ (sw & 1))) * 4) * 4);
+}
+
+__device__ __forceinline__ f32x4 lds4(uint32_t addr) {       // 16 bytes at a byte address of the dynamic LDS
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(smem) + addr);
+}
+
+// MFMA block of one step (32 channels of one offset; BF16: 64), specialised at compile time on WHICH of the wave's 32-row
+// tiles have the offset (LIVE bit m = tile m).  Every variant is straight-line code: fragments of sub-block kk+1 are fetched
+// from LDS while the MFMAs of sub-block kk run, so the MFMA stream never waits on an LDS round trip inside a step, also when
+// only part of the wave's rows take the offset (tiles on a boundary between two neighbour-mask groups).
+// a_addr[kk]: LDS byte address of my A fragment of sub-block kk in tile m = 0 (a_frag_offset inside the image being read);
+// w_addr: of my W fragment of sub-block 0, column tile n = 0 — lane constants in the buffer kernel, formed per step for the
+// current buffer in the 64-bit kernel.  BF16 (the buffer kernel alone): a 16-B fragment is 8 bf16 k-values and feeds ONE
+// v_mfma_f32_32x32x16_bf16 instead of four v_mfma_f32_32x32x2_f32.
+template <unsigned LIVE, int BN, bool BF16, int MT, int NT>
+__device__ __forceinline__ void mfma_step(f32x16 (&acc)[MT][NT], const uint32_t (&a_addr)[4], uint32_t w_addr) {
+    f32x4 av[2][MT], bv[2][NT];
+    // MFMA-issuing waves outrank the waves busy with DMA issue / address math on the same SIMD (+3-4 %)
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+        if ((LIVE >> m) & 1u) av[0][m] = lds4(a_addr[0] + 32 * m * A_LD_DMA * 4);
+#pragma unroll
+    for (int n = 0; n < NT; ++n) bv[0][n] = lds4(w_addr + 32 * n * 16);
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+        const int cb = kk & 1, nb = cb ^ 1;
+        if (kk + 1 < 4) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+                if ((LIVE >> m) & 1u) av[nb][m] = lds4(a_addr[kk + 1] + 32 * m * A_LD_DMA * 4);
+#pragma unroll
+            for (int n = 0; n < NT; ++n) bv[nb][n] = lds4(w_addr + (2 * (kk + 1) * BN + 32 * n) * 16);
+        }
+        if constexpr (BF16) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+                for (int n = 0; n < NT; ++n)
+                    if ((LIVE >> m) & 1u)
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av[cb][m]),
+                                                                            __builtin_bit_cast(bf16x8, bv[cb][n]), acc[m][n], 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int m = 0; m < MT; ++m)
+#pragma unroll
+                    for (int n = 0; n < NT; ++n)
+                        if ((LIVE >> m) & 1u)
+                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][m][s], bv[cb][n][s], acc[m][n], 0, 0, 0);
+        }
+    }
+    __builtin_amdgcn_s_setprio(0);
+}
+
+// bit m = this wave's 32-row tile m has offset k (wave-uniform: SGPR)
+template <int MT>
+__device__ __forceinline__ unsigned live_tiles(const uint32_t (&mmask)[MT], int k) {
+    unsigned live = 0;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) live |= ((mmask[m] >> k) & 1u) << m;
+    return live;
+}
+
+// The live-pattern dispatch: block(LIVE as an integral_constant) for the pattern `live` (live_tiles), nothing for 0
+template <int MT, class F>
+__device__ __forceinline__ void for_live_pattern(unsigned live, F&& block) {
+    if constexpr (MT == 1) {
+        if (live) block(std::integral_constant<unsigned, 1u>{});
+    } else {
+        static_assert(MT == 2, "live-pattern dispatch written for MT <= 2");
+        if (live == 3u) block(std::integral_constant<unsigned, 3u>{});
+        else if (live == 1u) block(std::integral_constant<unsigned, 1u>{});
+        else if (live == 2u) block(std::integral_constant<unsigned, 2u>{});
+    }
+}
+
+// Epilogue of a wave's MT x NT tiles (rows pos0 + 32 m .., column col0 + 32 n of lane r) through mfma32_row (common.h) and
+// conv_store.  The column test and the bias load stay outside the 16-register loop.
+template <int MT, int NT>
+__device__ __forceinline__ void conv_store_tiles(const ConvArgs& a, const f32x16 (&acc)[MT][NT], int64_t pos0, int col0, int h) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+            const int col = col0 + 32 * n;
+            if (col >= a.cout) continue;
+            const float bcol = conv_bias(a, col);
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int64_t pos = pos0 + 32 * m + 4 * h + mfma32_row(reg);
+                if (pos >= a.n_out) continue;
+                conv_store(a, a.order ? a.order[pos] : pos, col, acc[m][n][reg], bcol);
+            }
+        }
+    }
+}
+
 // 64-bit-addressed variant (operands of 4 GiB and more; PCC_CONV_PATH=global): both operands go global ->
 // LDS with global_load_lds_dwordx4 (no staging registers, no ds_write).  The A image is unpadded; each
 // 16-B slot p of row R holds global chunk p ^ ((R >> 1) & 7), the permutation being applied on the
@@ -165,37 +315,10 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
     const int CCH = a.cin / 32;
     const int K = a.K;
 
-    // which kernel offsets are live for this tile / for each of this wave's 32-row MFMA tiles
-    uint32_t tmask, mmask[MT];
-    {
-        const uint32_t all = (K >= 32) ? 0xffffffffu : ((1u << K) - 1u);
-        if (a.gmask) {
-            const int64_t g0 = row0 >> 5;
-            const int64_t ng = (a.n_out + 31) >> 5;
-            tmask = 0u;
-#pragma unroll
-            for (int g = 0; g < BM / 32; ++g) tmask |= (g0 + g < ng) ? (a.gmask[g0 + g] & all) : 0u;
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                const int64_t g = g0 + (wrow >> 5) + m;
-                const uint32_t v = (g < ng) ? (a.gmask[g] & all) : 0u;
-                mmask[m] = __builtin_amdgcn_readfirstlane(v);    // wave-uniform by construction
-            }
-        } else {
-            tmask = all;
-#pragma unroll
-            for (int m = 0; m < MT; ++m) mmask[m] = all;
-        }
-        tmask = __builtin_amdgcn_readfirstlane(tmask);
-    }
+    uint32_t mmask[MT];
+    const uint32_t tmask = conv_live_offsets<BM>(a, row0, wrow, mmask);
 
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.0f;
+    f32x16 acc[MT][NT] = {};
 
     // gather roles: 8 lanes per row (16 B each).  Register path: rows grow + 32 i.  DMA path: one
     // wave-instruction fills 1 KB = 8 consecutive rows, wave w issues instructions 4w .. 4w+3.
@@ -262,66 +385,20 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
         }
     };
 
-    // A-fragment addressing.  Lane (r, h) of a wave reads, for sub-block kk, the 16-B chunk 2 kk + h of
-    // row wrow + 32 m + r.  DMA image: physical slot = chunk ^ ((r >> 1) & 7), i.e. bit 0 -> h ^ (sw & 1)
-    // and bits 1-2 -> kk ^ (sw >> 1): four lane-constant offsets.
-    const int sw = (r >> 1) & 7;
-    int a_off[4];
+    // My fragments inside an image and a weight slab (lane constants); the buffer of the step is added per step: its
+    // number is a run-time value here, and a register array indexed by it would become scratch.
+    uint32_t a_lane[4];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk)
-        a_off[kk] = (((kk ^ (sw >> 1)) << 1) | (h ^ (sw & 1))) * 4;
-
-    // MFMA block of one step, specialised at compile time on WHICH of the wave's 32-row tiles have
-    // offset k (LIVE bit m = tile m).  Every variant is straight-line code: fragments of sub-block
-    // kk+1 are fetched from LDS while the MFMAs of sub-block kk run, so the MFMA stream never waits
-    // on an LDS round trip inside a step, also when only part of the wave's rows take the offset
-    // (tiles on a boundary between two neighbour-mask groups).
-    auto compute_live = [&](int buf, auto live_tag) {
-        constexpr unsigned LIVE = decltype(live_tag)::value;
-        const float* Ab = As + buf * A_ELEMS + (wrow + r) * A_LD;
-        const float* Wb = Ws + buf * W_ELEMS + (h * BN + wcol + r) * 4;
-        f32x4 av[2][MT], bv[2][NT];
-        // MFMA-issuing waves outrank the waves busy with DMA issue / address math on the same SIMD (+3-4 %)
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-            if ((LIVE >> m) & 1u) av[0][m] = *reinterpret_cast<const f32x4*>(Ab + 32 * m * A_LD + a_off[0]);
-#pragma unroll
-        for (int n = 0; n < NT; ++n) bv[0][n] = *reinterpret_cast<const f32x4*>(Wb + 32 * n * 4);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int cb = kk & 1, nb = cb ^ 1;
-            if (kk + 1 < 4) {
-#pragma unroll
-                for (int m = 0; m < MT; ++m)
-                    if ((LIVE >> m) & 1u) av[nb][m] = *reinterpret_cast<const f32x4*>(Ab + 32 * m * A_LD + a_off[kk + 1]);
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-                    bv[nb][n] = *reinterpret_cast<const f32x4*>(Wb + (2 * (kk + 1) * BN + 32 * n) * 4);
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int m = 0; m < MT; ++m)
-#pragma unroll
-                    for (int n = 0; n < NT; ++n)
-                        if ((LIVE >> m) & 1u)
-                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][m][s], bv[cb][n][s], acc[m][n], 0, 0, 0);
-        }
-        __builtin_amdgcn_s_setprio(0);
-    };
+    for (int kk = 0; kk < 4; ++kk) a_lane[kk] = a_frag_offset(wrow + r, h, kk);
+    const uint32_t w_lane = (uint32_t)((2 * A_ELEMS + (h * BN + wcol + r) * 4) * 4);
     auto compute = [&](int buf, int k) {
-        unsigned live = 0;
+        uint32_t a_addr[4];
 #pragma unroll
-        for (int m = 0; m < MT; ++m) live |= ((mmask[m] >> k) & 1u) << m;      // wave-uniform (SGPR)
-        if constexpr (MT == 1) {
-            if (live) compute_live(buf, std::integral_constant<unsigned, 1u>{});
-        } else {
-            static_assert(MT == 2, "live-pattern dispatch written for MT <= 2");
-            if (live == 3u) compute_live(buf, std::integral_constant<unsigned, 3u>{});
-            else if (live == 1u) compute_live(buf, std::integral_constant<unsigned, 1u>{});
-            else if (live == 2u) compute_live(buf, std::integral_constant<unsigned, 2u>{});
-        }
+        for (int kk = 0; kk < 4; ++kk) a_addr[kk] = a_lane[kk] + (uint32_t)(buf * A_ELEMS * 4);
+        const uint32_t w_addr = w_lane + (uint32_t)(buf * W_ELEMS * 4);
+        for_live_pattern<MT>(live_tiles(mmask, k), [&](auto live_tag) {
+            mfma_step<decltype(live_tag)::value, BN, false>(acc, a_addr, w_addr);
+        });
     };
 
     if (tmask != 0u) {
@@ -367,30 +444,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
         }
     }
 
-    // epilogue: D[row = (reg&3) + 8*(reg>>2) + 4*h][col = r] per 32x32 tile
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            const int col = nt * BN + wcol + 32 * n + r;
-            if (col >= a.cout) continue;
-            const float bcol = a.bias ? a.bias[col] : 0.0f;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int64_t pos = row0 + wrow + 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-                if (pos >= a.n_out) continue;
-                const int64_t row = a.order ? a.order[pos] : pos;
-                float v = acc[m][n][reg] + bcol;
-                if (a.film) {
-                    const float* fr = a.film + row * (2 * (int64_t)a.cout);
-                    v = v * fr[col] + fr[a.cout + col];
-                }
-                v = apply_act(v, a.act);
-                if (a.residual) v += a.residual[row * a.cout + col];
-                a.fout[row * a.cout + col] = v;
-            }
-        }
-    }
+    conv_store_tiles(a, acc, row0 + wrow, nt * BN + wcol + r, h);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -459,37 +513,10 @@ __global__ __launch_bounds__(256) void conv_mfma_buf_kernel(const ConvArgs a) {
     const int64_t row0 = tile * BM;
     const int K = a.K;
 
-    uint32_t tmask, mmask[MT];
-    {
-        const uint32_t all = (K >= 32) ? 0xffffffffu : ((1u << K) - 1u);
-        if (a.gmask) {
-            const int64_t g0 = row0 >> 5;
-            const int64_t ng = (a.n_out + 31) >> 5;
-            tmask = 0u;
-#pragma unroll
-            for (int g = 0; g < BM / 32; ++g) tmask |= (g0 + g < ng) ? (a.gmask[g0 + g] & all) : 0u;
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                const int64_t g = g0 + (wrow >> 5) + m;
-                const uint32_t v = (g < ng) ? (a.gmask[g] & all) : 0u;
-                mmask[m] = __builtin_amdgcn_readfirstlane(v);
-            }
-        } else {
-            tmask = all;
-#pragma unroll
-            for (int m = 0; m < MT; ++m) mmask[m] = all;
-        }
-        tmask = __builtin_amdgcn_readfirstlane(tmask);
-    }
+    uint32_t mmask[MT];
+    const uint32_t tmask = conv_live_offsets<BM>(a, row0, wrow, mmask);
 
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.0f;
-        }
+    f32x16 acc[MT][NT] = {};
 
     if (tmask != 0u) {
         __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
@@ -556,20 +583,17 @@ __global__ __launch_bounds__(256) void conv_mfma_buf_kernel(const ConvArgs a) {
                                                          w_voff[j], wso, 0, 0);
         };
 
-        // lane-constant LDS byte addresses of my fragments in both buffers.  Lane (r, h) reads, for
-        // sub-block kk, the 16-B chunk 2 kk + h of row wrow + 32 m + r; its slot is chunk ^ ((r >> 1) & 7).
-        const int sw = (r >> 1) & 7;
+        // lane-constant LDS byte addresses of my fragments in both buffers (a_frag_offset)
         uint32_t a_addr[2][4], w_addr[2];
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-                a_addr[b][kk] = (uint32_t)((b * A_ELEMS + (wrow + r) * 32 + (((kk ^ (sw >> 1)) << 1) | (h ^ (sw & 1))) * 4) * 4);
+            for (int kk = 0; kk < 4; ++kk) a_addr[b][kk] = (uint32_t)(b * A_ELEMS * 4) + a_frag_offset(wrow + r, h, kk);
             w_addr[b] = (uint32_t)((2 * A_ELEMS + b * W_ELEMS + (h * BN + wcol + r) * 4) * 4);
         }
-        auto lds4 = [&](uint32_t addr) { return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(smem) + addr); };
 
         // X3: lane (r, h) needs, for k16-step q, channels 16 q + 8 h .. + 7 of its rows = 16-B slots 4 q + 2 h and + 1
+        const int sw = (r >> 1) & 7;
         uint32_t a3_addr[2][2][2];
 #pragma unroll
         for (int b = 0; b < 2; ++b)
@@ -632,59 +656,11 @@ __global__ __launch_bounds__(256) void conv_mfma_buf_kernel(const ConvArgs a) {
             }
             __builtin_amdgcn_s_setprio(0);
         };
-        auto compute_live = [&](auto bufc, auto live_tag) {
-            if constexpr (X3) {
-                compute_live_x3(bufc, live_tag);
-                return;
-            }
-            constexpr int buf = decltype(bufc)::value;
-            constexpr unsigned LIVE = decltype(live_tag)::value;
-            f32x4 av[2][MT], bv[2][NT];
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-                if ((LIVE >> m) & 1u) av[0][m] = lds4(a_addr[buf][0] + 32 * m * 32 * 4);
-#pragma unroll
-            for (int n = 0; n < NT; ++n) bv[0][n] = lds4(w_addr[buf] + 32 * n * 16);
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const int cb = kk & 1, nb = cb ^ 1;
-                if (kk + 1 < 4) {
-#pragma unroll
-                    for (int m = 0; m < MT; ++m)
-                        if ((LIVE >> m) & 1u) av[nb][m] = lds4(a_addr[buf][kk + 1] + 32 * m * 32 * 4);
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) bv[nb][n] = lds4(w_addr[buf] + (2 * (kk + 1) * BN + 32 * n) * 16);
-                }
-                if constexpr (BF16) {
-#pragma unroll
-                    for (int m = 0; m < MT; ++m)
-#pragma unroll
-                        for (int n = 0; n < NT; ++n)
-                            if ((LIVE >> m) & 1u)
-                                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av[cb][m]),
-                                                                                    __builtin_bit_cast(bf16x8, bv[cb][n]), acc[m][n], 0, 0, 0);
-                } else {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s)
-#pragma unroll
-                        for (int m = 0; m < MT; ++m)
-#pragma unroll
-                            for (int n = 0; n < NT; ++n)
-                                if ((LIVE >> m) & 1u)
-                                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][m][s], bv[cb][n][s], acc[m][n], 0, 0, 0);
-                }
-            }
-            __builtin_amdgcn_s_setprio(0);
-        };
-        auto compute = [&](auto bufc, unsigned live) {        // live: wave-uniform, bit m = 32-row tile m has this offset
-            if constexpr (MT == 1) {
-                if (live) compute_live(bufc, std::integral_constant<unsigned, 1u>{});
-            } else {
-                if (live == 3u) compute_live(bufc, std::integral_constant<unsigned, 3u>{});
-                else if (live == 1u) compute_live(bufc, std::integral_constant<unsigned, 1u>{});
-                else if (live == 2u) compute_live(bufc, std::integral_constant<unsigned, 2u>{});
-            }
+        auto compute = [&](auto bufc, unsigned live) {        // live: live_tiles of the step's offset
+            for_live_pattern<MT>(live, [&](auto live_tag) {
+                if constexpr (X3) compute_live_x3(bufc, live_tag);
+                else mfma_step<decltype(live_tag)::value, BN, BF16>(acc, a_addr[decltype(bufc)::value], w_addr[decltype(bufc)::value]);
+            });
         };
 
         // One kernel offset = CCH steps of straight-line code.  Step c computes chunk c from buffer
@@ -700,9 +676,7 @@ __global__ __launch_bounds__(256) void conv_mfma_buf_kernel(const ConvArgs a) {
             const int knext = rem ? __builtin_ctz(rem) : -1;
             const uint32_t rem2 = rem & (rem - 1u);
             const int kn2 = rem2 ? __builtin_ctz(rem2) : (knext >= 0 ? knext : k);
-            unsigned live = 0;
-#pragma unroll
-            for (int m = 0; m < MT; ++m) live |= ((mmask[m] >> k) & 1u) << m;
+            const unsigned live = live_tiles(mmask, k);
             static_for<0, CCH>([&](auto cc) {
                 constexpr int c = decltype(cc)::value;
                 constexpr int buf = (P + c) & 1;
@@ -735,30 +709,7 @@ __global__ __launch_bounds__(256) void conv_mfma_buf_kernel(const ConvArgs a) {
         }
     }
 
-    // epilogue: D[row = (reg&3) + 8*(reg>>2) + 4*h][col = r] per 32x32 tile
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int col = nt * BN + wcol + 32 * n + r;
-                if (col >= a.cout) continue;
-                const float bcol = a.bias ? a.bias[col] : 0.0f;
-                const int64_t pos = row0 + wrow + 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-                if (pos >= a.n_out) continue;
-                const int64_t row = a.order ? a.order[pos] : pos;
-                float v = acc[m][n][reg] + bcol;
-                if (a.film) {
-                    const float* fr = a.film + row * (2 * (int64_t)a.cout);
-                    v = v * fr[col] + fr[a.cout + col];
-                }
-                v = apply_act(v, a.act);
-                if (a.residual) v += a.residual[row * a.cout + col];
-                a.fout[row * a.cout + col] = v;
-            }
-        }
-    }
+    conv_store_tiles(a, acc, row0 + wrow, nt * BN + wcol + r, h);
 #endif
 }
 
@@ -975,20 +926,12 @@ __global__ __launch_bounds__(512) void conv_small_kernel(const ConvArgs a) {
     // epilogue: register e = D[row 4 (lane >> 4) + e][column lane & 15] of my 16 x 16 block
     const int col = nt * 32 + wcol + j16;
     if (col < a.cout) {
-        const float bcol = a.bias ? a.bias[col] : 0.0f;
+        const float bcol = conv_bias(a, col);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int64_t pos = row0 + wrow + 4 * kq + e;
             if (pos >= a.n_out) continue;
-            const int64_t row = a.order ? a.order[pos] : pos;
-            float v = acc[e] + bcol;
-            if (a.film) {
-                const float* fr = a.film + row * (2 * (int64_t)a.cout);
-                v = v * fr[col] + fr[a.cout + col];
-            }
-            v = apply_act(v, a.act);
-            if (a.residual) v += a.residual[row * a.cout + col];
-            a.fout[row * a.cout + col] = v;
+            conv_store(a, a.order ? a.order[pos] : pos, col, acc[e], bcol);
         }
     }
 #endif
@@ -1040,16 +983,7 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(const ConvArgs a) {
             }
         }
 #pragma unroll
-        for (int j = 0; j < CPT; ++j) {
-            float v = acc[j] + (a.bias ? a.bias[co + j] : 0.0f);
-            if (a.film) {
-                const float* fr = a.film + row * (2 * (int64_t)cout);
-                v = v * fr[co + j] + fr[cout + co + j];
-            }
-            v = apply_act(v, a.act);
-            if (a.residual) v += a.residual[row * cout + co + j];
-            a.fout[row * cout + co + j] = v;
-        }
+        for (int j = 0; j < CPT; ++j) conv_store(a, row, co + j, acc[j], conv_bias(a, co + j));
     }
 }
 
@@ -1425,6 +1359,19 @@ static int conv_fwd(ConvMode mode, const ConvArgs& a, void* stream) {
     }
 }
 
+// The three weight packings: `kern` lays W [K, cin, cout] out for its kernel, cin zero-padded to a multiple of `cin_pad`
+template <class T>
+static int pack_weights(const char* who, void (*kern)(const float*, int, int, int, int, int, T*), int cin_pad, const float* w,
+                        int K, int cin, int cout, T* w_packed, void* stream) {
+    PCC_REQUIRE(K >= 1 && cin >= 1 && cout >= 1, "%s: bad shape", who);
+    const int cinp = (cin + cin_pad - 1) / cin_pad * cin_pad, coutp = round_up32(cout);
+    const int64_t total = (int64_t)K * cinp * coutp;
+    hipLaunchKernelGGL(kern, dim3(blocks_for(total, 256, 4096)), dim3(256), 0, as_stream(stream), w, K, cin, cout, cinp, coutp,
+                       w_packed);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
 }  // namespace pcc
 
 using namespace pcc;
@@ -1436,13 +1383,7 @@ int64_t pcc_conv_packed_elems(int32_t K, int32_t cin, int32_t cout) {
 }
 
 int pcc_conv_pack_weights(const float* w, int32_t K, int32_t cin, int32_t cout, float* w_packed, void* stream) {
-    PCC_REQUIRE(K >= 1 && cin >= 1 && cout >= 1, "pcc_conv_pack_weights: bad shape");
-    const int cinp = round_up32(cin), coutp = round_up32(cout);
-    const int64_t total = (int64_t)K * cinp * coutp;
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks_for(total, 256, 4096)), dim3(256), 0, as_stream(stream), w, K, cin,
-                       cout, cinp, coutp, w_packed);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    return pack_weights("pcc_conv_pack_weights", pack_weights_kernel, 32, w, K, cin, cout, w_packed, stream);
 }
 
 int64_t pcc_conv_packed_elems_bf16(int32_t K, int32_t cin, int32_t cout) {
@@ -1450,20 +1391,15 @@ int64_t pcc_conv_packed_elems_bf16(int32_t K, int32_t cin, int32_t cout) {
 }
 
 int pcc_conv_pack_weights_bf16(const float* w, int32_t K, int32_t cin, int32_t cout, uint16_t* w_packed, void* stream) {
-    PCC_REQUIRE(K >= 1 && cin >= 1 && cout >= 1, "pcc_conv_pack_weights_bf16: bad shape");
-    const int cinp = (cin + 63) / 64 * 64, coutp = round_up32(cout);
-    const int64_t total = (int64_t)K * cinp * coutp;
-    hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(blocks_for(total, 256, 4096)), dim3(256), 0, as_stream(stream), w, K, cin,
-                       cout, cinp, coutp, reinterpret_cast<__bf16*>(w_packed));
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    return pack_weights("pcc_conv_pack_weights_bf16", pack_weights_bf16_kernel, 64, w, K, cin, cout,
+                        reinterpret_cast<__bf16*>(w_packed), stream);
 }
 
 int pcc_conv_fwd_bf16(const uint16_t* fin, int64_t n_in, int32_t cin, const uint16_t* w_packed, const float* bias, const int32_t* nbr,
                       const int32_t* order, const uint32_t* group_mask32, int32_t K, float* fout, int64_t n_out, int32_t cout,
                       int32_t act, const float* film, const float* residual, void* stream) {
     return conv_fwd(CONV_BF16, {reinterpret_cast<const float*>(fin), nullptr, reinterpret_cast<const float*>(w_packed), bias, nbr, order,
-                                group_mask32, fout, film, residual, n_in, n_out, cin, cout, round_up32(cout), K, act, 1}, stream);
+                                group_mask32, fout, film, residual, n_in, n_out, cin, cout, round_up32(cout), K, act}, stream);
 }
 
 int64_t pcc_conv_packed_elems_x3(int32_t K, int32_t cin, int32_t cout) {
@@ -1471,20 +1407,14 @@ int64_t pcc_conv_packed_elems_x3(int32_t K, int32_t cin, int32_t cout) {
 }
 
 int pcc_conv_pack_weights_x3(const float* w, int32_t K, int32_t cin, int32_t cout, uint16_t* w_packed, void* stream) {
-    PCC_REQUIRE(K >= 1 && cin >= 1 && cout >= 1, "pcc_conv_pack_weights_x3: bad shape");
-    const int cinp = round_up32(cin), coutp = round_up32(cout);
-    const int64_t total = (int64_t)K * cinp * coutp;
-    hipLaunchKernelGGL(pack_weights_x3_kernel, dim3(blocks_for(total, 256, 4096)), dim3(256), 0, as_stream(stream), w, K, cin,
-                       cout, cinp, coutp, w_packed);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    return pack_weights("pcc_conv_pack_weights_x3", pack_weights_x3_kernel, 32, w, K, cin, cout, w_packed, stream);
 }
 
 int pcc_conv_fwd_x3(const float* fin, int64_t n_in, int32_t cin, const uint16_t* w_packed, const float* bias, const int32_t* nbr,
                     const int32_t* order, const uint32_t* group_mask32, int32_t K, float* fout, int64_t n_out, int32_t cout,
                     int32_t act, const float* film, const float* residual, void* stream) {
     return conv_fwd(CONV_X3, {fin, nullptr, reinterpret_cast<const float*>(w_packed), bias, nbr, order, group_mask32, fout, film,
-                              residual, n_in, n_out, cin, cout, round_up32(cout), K, act, 0}, stream);
+                              residual, n_in, n_out, cin, cout, round_up32(cout), K, act}, stream);
 }
 
 int pcc_im2col_thin(const float* fin, int32_t cin, const int32_t* nbr, int64_t n_out, int32_t K, float* out, int32_t k2,
@@ -1531,7 +1461,7 @@ int pcc_conv_fwd(const float* fin, int64_t n_in, int32_t cin, const float* w, co
                  const int32_t* nbr, const int32_t* order, const uint32_t* group_mask32, int32_t K, float* fout,
                  int64_t n_out, int32_t cout, int32_t act, const float* film, const float* residual, void* stream) {
     return conv_fwd(CONV_F32, {fin, w, w_packed, bias, nbr, order, group_mask32, fout, film, residual, n_in, n_out, cin, cout,
-                               round_up32(cout), K, act, 0}, stream);
+                               round_up32(cout), K, act}, stream);
 }
 
 int pcc_conv_kernel_name(int32_t mode, int64_t n_in, int32_t cin, int32_t cout, int64_t n_out, int32_t K, int32_t has_nbr,

@@ -23,7 +23,6 @@
 
 namespace pcc {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int WG_SPLIT_MAX = 128;     // row-group splits per (offset, weight block): the grid must be many times the chip
@@ -64,6 +63,16 @@ struct WgradArgs {
     int split;               // row-group splits (MFMA kernel)
 };
 
+// A wave's 32 x 32 accumulator tile (mfma32_row, common.h: row = input channel, col = output channel) -> rows ci0 .. ci0 + 31,
+// column `co` (this lane's: tile column + r) of the partial image P [cin][cout]
+__device__ __forceinline__ void store_partial_tile(const f32x16& acc, float* P, int cout, int ci0, int co, int h) {
+    // one address per lane, the registers at wave-uniform distances from it: sixteen (row x cout) products, as 64-bit values in
+    // vector registers across the stores, cost the slice kernels a wave per SIMD
+    float* p = P + (int64_t)(ci0 + 4 * h) * cout + co;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) p[(int64_t)mfma32_row(reg) * cout] = acc[reg];
+}
+
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -86,13 +95,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
     const int cw = rowsplit ? (wave_u & 1) : wave_u;                                      // chunk this wave stages
     const int slotA = rowsplit ? 2 * (wave_u >> 1) : 2 * wm, slotB = rowsplit ? 2 * (wave_u >> 1) : 2 * wn;
 
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.0f;
+    f32x16 acc[2][2] = {};
 
     __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.fin), 0, (int)(uint32_t)(a.n_in * a.cin * 4), WG_FLAGS);
     __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0, (int)(uint32_t)(a.n_out * a.cout * 4), WG_FLAGS);
@@ -175,7 +178,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
         __syncthreads();
     }
 
-    // D[row = (reg & 3) + 8 (reg >> 2) + 4 h][col = r] of each 32 x 32 tile: row = input channel, col = output channel
     float* P = a.partial + ((int64_t)(rowsplit ? s * 4 + wave_u : s) * a.K + k) * a.cin * a.cout;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -183,12 +185,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
             if (!live_n[n]) continue;
-            const int co = cout0 + (2 * wn + n) * 32 + r;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int ci = cin0 + (2 * wm + m) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-                P[(int64_t)ci * a.cout + co] = acc[m][n][reg];
-            }
+            store_partial_tile(acc[m][n], P, a.cout, cin0 + (2 * wm + m) * 32, cout0 + (2 * wn + n) * 32 + r, h);
         }
     }
 #endif
@@ -229,11 +226,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_slice_kernel(const WgradArgs a
     const bool tile_live = tm < cbi && tn < cbo;
     const int cw = wave_u & 1, rh = wave_u >> 1;                  // my DMA role: chunk cw, rows 16 rh .. 16 rh + 15
 
-    f32x16 acc[O];
-#pragma unroll
-    for (int o = 0; o < O; ++o)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[o][i] = 0.0f;
+    f32x16 acc[O] = {};
 
     __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.fin), 0, (int)(uint32_t)(a.n_in * a.cin * 4), WG_FLAGS);
     __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0, (int)(uint32_t)(a.n_out * a.cout * 4), WG_FLAGS);
@@ -381,13 +374,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_slice_kernel(const WgradArgs a
 #pragma unroll
     for (int o = 0; o < O; ++o) {
         if (k0 + o >= a.K) break;
-        float* P = a.partial + ((int64_t)s * a.K + (k0 + o)) * a.cin * a.cout;
-        const int co = tn * 32 + r;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int ci = tm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-            P[(int64_t)ci * a.cout + co] = acc[o][reg];
-        }
+        store_partial_tile(acc[o], a.partial + ((int64_t)s * a.K + (k0 + o)) * a.cin * a.cout, a.cout, tm * 32, tn * 32 + r, h);
     }
 #endif
 }
@@ -408,6 +395,15 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 
+// One MFMA operand (8 k-values = image rows of my column) from two transposing reads, 4 rows each: `p` = my address inside the
+// first 4-row block (tr_off below), the second block four 128-B rows on
+__device__ __forceinline__ bf16x8 tr_operand(const unsigned short* p) {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p + 4 * 64));
+    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8, v);
+}
+
 __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const WgradArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -425,11 +421,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const WgradArgs a)
     // 0 / 2 stage the first group's X / dY, waves 1 / 3 the second's), doubling the MFMA work per barrier pair
     const bool two_groups = cbi == 1 && cbo == 1;
 
-    f32x16 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[i][j] = 0.0f;
+    f32x16 acc[4] = {};
 
     __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.fin), 0, (int)(uint32_t)(a.n_in * a.cin * 2), WG_FLAGS);
     __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0, (int)(uint32_t)(a.n_out * a.cout * 2), WG_FLAGS);
@@ -499,19 +491,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const WgradArgs a)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (!live[i]) continue;                         // wave-uniform: EXEC stays all ones for the transposing reads
-                const unsigned short* ap = As + ((tm[i] >> 1) + gs) * 2048 + row0 * 64 + (tm[i] & 1) * 32 + tr_off;
-                const s16x4 alo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(ap));
-                const s16x4 ahi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(ap + 4 * 64));
-                const s16x8 a8 = {alo[0], alo[1], alo[2], alo[3], ahi[0], ahi[1], ahi[2], ahi[3]};
+                const bf16x8 aop = tr_operand(As + ((tm[i] >> 1) + gs) * 2048 + row0 * 64 + (tm[i] & 1) * 32 + tr_off);
                 if (tn[i] != bn_loaded) {                      // 128 x 128: all of the wave's tiles share n
-                    const unsigned short* bp = Bs + ((tn[i] >> 1) + gs) * 2048 + row0 * 64 + (tn[i] & 1) * 32 + tr_off;
-                    const s16x4 blo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(bp));
-                    const s16x4 bhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(bp + 4 * 64));
-                    const s16x8 b8 = {blo[0], blo[1], blo[2], blo[3], bhi[0], bhi[1], bhi[2], bhi[3]};
-                    bop = __builtin_bit_cast(bf16x8, b8);
+                    bop = tr_operand(Bs + ((tn[i] >> 1) + gs) * 2048 + row0 * 64 + (tn[i] & 1) * 32 + tr_off);
                     bn_loaded = tn[i];
                 }
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a8), bop, acc[i], 0, 0, 0);
+                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aop, bop, acc[i], 0, 0, 0);
             }
         }
         __syncthreads();
@@ -522,12 +507,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const WgradArgs a)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         if (!live[i]) continue;
-        const int co = cout0 + tn[i] * 32 + r;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int ci = cin0 + tm[i] * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-            P[(int64_t)ci * a.cout + co] = acc[i][reg];
-        }
+        store_partial_tile(acc[i], P, a.cout, cin0 + tm[i] * 32, cout0 + tn[i] * 32 + r, h);
     }
 #endif
 }
@@ -558,11 +538,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_slice_kernel(const WgradA
     const uint32_t set_mask = (((1u << O) - 1u) << k0) & ((1u << a.K) - 1u);
     const int tm = wave_u >> 1, tn = wave_u & 1;
 
-    f32x16 acc[O];
-#pragma unroll
-    for (int o = 0; o < O; ++o)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[o][j] = 0.0f;
+    f32x16 acc[O] = {};
 
     __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.fin), 0, (int)(uint32_t)(a.n_in * a.cin * 2), WG_FLAGS);
     __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0, (int)(uint32_t)(a.n_out * a.cout * 2), WG_FLAGS);
@@ -597,19 +573,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_slice_kernel(const WgradA
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 const int row0 = 16 * ks + 8 * h;
-                const unsigned short* bp = Ys + row0 * 64 + tn * 32 + tr_off;
-                const s16x4 blo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(bp));
-                const s16x4 bhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(bp + 4 * 64));
-                const s16x8 b8 = {blo[0], blo[1], blo[2], blo[3], bhi[0], bhi[1], bhi[2], bhi[3]};
-                const bf16x8 bop = __builtin_bit_cast(bf16x8, b8);
+                const bf16x8 bop = tr_operand(Ys + row0 * 64 + tn * 32 + tr_off);
 #pragma unroll
                 for (int o = 0; o < O; ++o) {
                     if (!((rem >> o) & 1u)) continue;                       // wave-uniform: EXEC stays all ones
-                    const unsigned short* ap = Xs + o * 2048 + row0 * 64 + tm * 32 + tr_off;
-                    const s16x4 alo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(ap));
-                    const s16x4 ahi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(ap + 4 * 64));
-                    const s16x8 a8 = {alo[0], alo[1], alo[2], alo[3], ahi[0], ahi[1], ahi[2], ahi[3]};
-                    acc[o] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a8), bop, acc[o], 0, 0, 0);
+                    acc[o] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(Xs + o * 2048 + row0 * 64 + tm * 32 + tr_off), bop, acc[o], 0, 0, 0);
                 }
             }
             __syncthreads();
@@ -619,13 +587,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_slice_kernel(const WgradA
 #pragma unroll
     for (int o = 0; o < O; ++o) {
         if (k0 + o >= a.K) break;
-        float* P = a.partial + ((int64_t)s * a.K + (k0 + o)) * a.cin * a.cout;
-        const int co = tn * 32 + r;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int ci = tm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-            P[(int64_t)ci * a.cout + co] = acc[o][reg];
-        }
+        store_partial_tile(acc[o], a.partial + ((int64_t)s * a.K + (k0 + o)) * a.cin * a.cout, a.cout, tm * 32, tn * 32 + r, h);
     }
 #endif
 }
@@ -856,29 +818,45 @@ int pcc_conv_wgrad_kernel_name(int32_t bf16, int32_t K, int32_t cin, int32_t cou
     return PCC_OK;
 }
 
-int pcc_conv_wgrad(const float* fin, int64_t n_in, int32_t cin, const float* dy, int64_t n_out, int32_t cout, const int32_t* nbr,
-                   const int32_t* order, const uint32_t* group_mask32, int32_t K, float* dw, float* scratch, int64_t scratch_elems,
-                   void* stream) {
-    PCC_REQUIRE(K >= 1 && K <= 27 && cin >= 1 && cout >= 1, "pcc_conv_wgrad: bad shape");
-    PCC_REQUIRE(nbr != nullptr, "pcc_conv_wgrad: neighbour table required (kernel_size 1: pass the identity map)");
-    PCC_REQUIRE(scratch_elems >= pcc_conv_wgrad_scratch_elems(K, cin, cout), "pcc_conv_wgrad: scratch too small");
+// The weight gradient of both entries: checks, plan, launch, reduce.  The fp32 entry looks at its shape, map and scratch (the
+// bound of pcc_conv_wgrad_scratch_elems) first and at its operands only when there are rows and an MFMA kernel to run; the
+// bf16 entry plans first, checks its operands whatever the row count, and bounds the scratch by what its plan writes.
+// (bf16: fin and dy hold bf16, as in WgradArgs.)
+static int wgrad(bool bf16, const float* fin, int64_t n_in, int cin, const float* dy, int64_t n_out, int cout, const int32_t* nbr,
+                 const int32_t* order, const uint32_t* gmask, int K, float* dw, float* scratch, int64_t scratch_elems, void* stream) {
+    const char* who = bf16 ? "pcc_conv_wgrad_bf16" : "pcc_conv_wgrad";
+    const uint64_t esz = bf16 ? 2 : 4;
+    WgradPlan p;
+    auto check_operands = [&]() -> int {       // what the LDS-DMA kernels need of the gathered tensors
+        PCC_REQUIRE((uint64_t)n_in * cin * esz <= WG_OOB && (uint64_t)n_out * cout * esz <= WG_OOB,
+                    "%s: operands of 4 GiB and more are not supported", who);
+        PCC_REQUIRE(((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0,
+                    "%s: fin and dy must be 16-byte aligned (16-byte LDS-DMA loads)", who);
+        return PCC_OK;
+    };
+    if (bf16) {
+        if (int rc = plan_wgrad(true, K, cin, cout, n_out, p)) return rc;
+        PCC_REQUIRE(nbr != nullptr, "%s: neighbour table required", who);
+        if (int rc = check_operands()) return rc;
+    } else {
+        PCC_REQUIRE(K >= 1 && K <= 27 && cin >= 1 && cout >= 1, "%s: bad shape", who);
+        PCC_REQUIRE(nbr != nullptr, "%s: neighbour table required (kernel_size 1: pass the identity map)", who);
+        PCC_REQUIRE(scratch_elems >= pcc_conv_wgrad_scratch_elems(K, cin, cout), "%s: scratch too small", who);
+    }
     hipStream_t st = as_stream(stream);
     const int64_t elems = (int64_t)K * cin * cout;
     if (n_out <= 0) {
         PCC_CHECK_HIP(hipMemsetAsync(dw, 0, (size_t)elems * sizeof(float), st));
         return PCC_OK;
     }
-    WgradPlan p;
-    if (int rc = plan_wgrad(false, K, cin, cout, n_out, p)) return rc;
-    WgradArgs a;
-    a.fin = fin; a.dy = dy; a.nbr = nbr; a.order = order; a.gmask = group_mask32; a.partial = scratch;
-    a.n_in = n_in; a.n_out = n_out; a.cin = cin; a.cout = cout; a.K = K; a.split = p.split;
-    if (p.family != WGF_THIN) {
-        PCC_REQUIRE((uint64_t)n_in * cin * 4 <= WG_OOB && (uint64_t)n_out * cout * 4 <= WG_OOB,
-                    "pcc_conv_wgrad: operands of 4 GiB and more are not supported yet");
-        PCC_REQUIRE(((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0,
-                    "pcc_conv_wgrad: fin and dy must be 16-byte aligned (16-byte LDS-DMA loads)");
+    if (bf16) {
+        PCC_REQUIRE(scratch_elems >= (int64_t)p.partials * elems, "%s: scratch too small", who);
+    } else {
+        if (int rc = plan_wgrad(false, K, cin, cout, n_out, p)) return rc;
+        if (p.family != WGF_THIN)
+            if (int rc = check_operands()) return rc;
     }
+    const WgradArgs a = {fin, dy, nbr, order, gmask, scratch, n_in, n_out, cin, cout, K, p.split};
     if (p.family == WGF_SLICE) {
 #define PCC_SLICE(OO)                                                                                                              \
     do {                                                                                                                           \
@@ -892,50 +870,35 @@ int pcc_conv_wgrad(const float* fin, int64_t n_in, int32_t cin, const float* dy,
         else if (p.O == 9) PCC_SLICE(9);
         else PCC_SLICE(5);
 #undef PCC_SLICE
-    } else if (p.family == WGF_ONE) {
-        const dim3 grid((unsigned)(K * a.split), (unsigned)((cin + 127) / 128), (unsigned)((cout + 127) / 128));
-        hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 8 * 1024 * sizeof(float), st, a);
-    } else {
+    } else if (p.family == WGF_BF16_SLICE) {
+        const unsigned sets = (unsigned)((K + p.O - 1) / p.O);
+        const size_t lds = (size_t)(p.O + 1) * 2048 * sizeof(unsigned short);
+        if (p.O == 3) hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<3>, dim3(sets * a.split), dim3(256), lds, st, a);
+        else if (p.O == 5) hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<5>, dim3(sets * a.split), dim3(256), lds, st, a);
+        else hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<9>, dim3(sets * a.split), dim3(256), lds, st, a);
+    } else if (p.family == WGF_THIN) {
         hipLaunchKernelGGL(conv_wgrad_thin_kernel, dim3((unsigned)(K * WG_SPLIT_THIN)), dim3(256), 0, st, a);
+    } else {                                  // one offset and one block of up to 128 x 128 of W[k] per workgroup
+        const dim3 grid((unsigned)(K * a.split), (unsigned)((cin + 127) / 128), (unsigned)((cout + 127) / 128));
+        if (p.family == WGF_BF16_ONE) hipLaunchKernelGGL(conv_wgrad_bf16_kernel, grid, dim3(256), 4 * 2048 * sizeof(unsigned short), st, a);
+        else hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 8 * 1024 * sizeof(float), st, a);
     }
     launch_wgrad_reduce(scratch, elems, p.partials, dw, st);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
 }
 
+int pcc_conv_wgrad(const float* fin, int64_t n_in, int32_t cin, const float* dy, int64_t n_out, int32_t cout, const int32_t* nbr,
+                   const int32_t* order, const uint32_t* group_mask32, int32_t K, float* dw, float* scratch, int64_t scratch_elems,
+                   void* stream) {
+    return wgrad(false, fin, n_in, cin, dy, n_out, cout, nbr, order, group_mask32, K, dw, scratch, scratch_elems, stream);
+}
+
 int pcc_conv_wgrad_bf16(const uint16_t* fin, int64_t n_in, int32_t cin, const uint16_t* dy, int64_t n_out, int32_t cout,
                         const int32_t* nbr, const int32_t* order, const uint32_t* group_mask32, int32_t K, float* dw, float* scratch,
                         int64_t scratch_elems, void* stream) {
-    WgradPlan p;
-    if (int rc = plan_wgrad(true, K, cin, cout, n_out, p)) return rc;
-    PCC_REQUIRE(nbr != nullptr, "pcc_conv_wgrad_bf16: neighbour table required");
-    PCC_REQUIRE((uint64_t)n_in * cin * 2 <= WG_OOB && (uint64_t)n_out * cout * 2 <= WG_OOB, "pcc_conv_wgrad_bf16: operands of 4 GiB and more are not supported");
-    PCC_REQUIRE(((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0,
-                "pcc_conv_wgrad_bf16: fin and dy must be 16-byte aligned (16-byte LDS-DMA loads)");
-    hipStream_t st = as_stream(stream);
-    const int64_t elems = (int64_t)K * cin * cout;
-    if (n_out <= 0) {
-        PCC_CHECK_HIP(hipMemsetAsync(dw, 0, (size_t)elems * sizeof(float), st));
-        return PCC_OK;
-    }
-    WgradArgs a;
-    a.fin = reinterpret_cast<const float*>(fin); a.dy = reinterpret_cast<const float*>(dy); a.nbr = nbr; a.order = order;
-    a.gmask = group_mask32; a.partial = scratch; a.n_in = n_in; a.n_out = n_out; a.cin = cin; a.cout = cout; a.K = K;
-    a.split = p.split;
-    PCC_REQUIRE(scratch_elems >= (int64_t)p.partials * elems, "pcc_conv_wgrad_bf16: scratch too small");
-    if (p.family == WGF_BF16_SLICE) {
-        const unsigned sets = (unsigned)((K + p.O - 1) / p.O);
-        const size_t lds = (size_t)(p.O + 1) * 2048 * sizeof(unsigned short);
-        if (p.O == 3) hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<3>, dim3(sets * a.split), dim3(256), lds, st, a);
-        else if (p.O == 5) hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<5>, dim3(sets * a.split), dim3(256), lds, st, a);
-        else hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<9>, dim3(sets * a.split), dim3(256), lds, st, a);
-    } else {
-        const dim3 grid((unsigned)(K * a.split), (unsigned)((cin + 127) / 128), (unsigned)((cout + 127) / 128));
-        hipLaunchKernelGGL(conv_wgrad_bf16_kernel, grid, dim3(256), 4 * 2048 * sizeof(unsigned short), st, a);
-    }
-    launch_wgrad_reduce(scratch, elems, p.partials, dw, st);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    return wgrad(true, reinterpret_cast<const float*>(fin), n_in, cin, reinterpret_cast<const float*>(dy), n_out, cout, nbr, order,
+                 group_mask32, K, dw, scratch, scratch_elems, stream);
 }
 
 }  // extern "C"
