@@ -1,5 +1,16 @@
-// Per-batch top-k occupancy selection (GenerativeUpBlock._topk_prediction, model/blocks.py:130-150)
-// and canonical coordinate sort (utils.sort_tensor / sort_points, utils.py:155-204).
+// Which voxels a decoder keeps and the order in which the rows of a kernel map run.  What the file holds, in order:
+//   top-k            per-batch occupancy selection (GenerativeUpBlock._topk_prediction, model/blocks.py:130-150), pcc_topk_mask.
+//                    Pieces: key_digit, topk_state_init, topk_pick_step (one round's pick: all four pick sites), topk_rounds
+//                    (zero, histogram, pick over a range of passes in one workgroup).  Launch paths: generic (topk_init,
+//                    topk_hist + topk_pick per pass), one item (topk_hist1_kernel + topk_pick1_kernel over the logit bytes,
+//                    topk_tail_kernel for the tie-break bytes), one small item (topk_small_kernel); topk_write_mask.
+//   execution order  rows sorted by neighbour mask, rarest offset first, pcc_order_rows_by_mask: offset counts, keys
+//                    (32-bit, or 64-bit under spatial blocks), the radix sort of sort.hip, tile_or_mask per 32 positions;
+//                    order_small_body = counts + keys + sort in one workgroup (order_small_kernel)
+//   small map        small_map_kernel: probes, row masks, order_small_body and group masks in ONE launch, pcc_small_kernel_map
+//   row permutation  permute_rows_kernel, pcc_permute_map_rows
+//   canonical sort   (b, x, y, z) order of coordinates (utils.sort_tensor / sort_points, utils.py:155-204), pcc_sort_coords;
+//                    pcc_sort_scratch_bytes and the ONE layout of that scratch (SortScratch), shared with the execution order
 //
 // top-k = MSB-first radix select over a 96-bit composite key
 //     hi32 = order-preserving map of the fp32 logit (NaN on top, as torch.topk)
@@ -53,16 +64,48 @@ __device__ __forceinline__ int cmp_prefix(const Key96& k, const int32_t* st, int
     return 0;
 }
 
+// byte `pass` (0 = most significant) of the key: the digit of radix pass `pass`
+__device__ __forceinline__ uint32_t key_digit(const Key96& k, int pass) { return (k.w[pass >> 2] >> (8 * (3 - (pass & 3)))) & 0xFFu; }
+
+// the state words of an item before pass 0 (st[0..7] otherwise zero): k rows to find
+__device__ __forceinline__ void topk_state_init(int32_t* st, int k) {
+    st[0] = k;
+    if (k <= 0) { st[1] = 1; st[2] = 13; }  // select nothing
+}
+
+// One round's pick: from the 256-bin histogram `h` (LDS) of the rows that match the prefix so far, find the bin that holds the
+// k-th largest key, append it to the prefix and say whether the item is resolved.  `st`: the item's state words, in LDS or in
+// global memory.  EVERY thread of the workgroup calls it (one barrier inside); thread `d` < 256 of the `picker` threads owns bin d.
+__device__ __forceinline__ void topk_pick_step(const int* h, int32_t* st, int pass, int d, bool picker, int* total_s) {
+    const int krem = st[0];
+    int above = 0, mine = 0;
+    if (picker) {
+        mine = h[d];
+        for (int j = d + 1; j < 256; ++j) above += h[j];
+        if (d == 0) *total_s = above + mine;
+    }
+    __syncthreads();      // every thread has read krem and h: the owner of the boundary bin writes after this
+    if (pass == 0 && *total_s <= krem) {
+        // the item has no more than k rows: keep them all (compare zero prefix bytes)
+        if (picker && d == 0) { st[1] = 1; st[2] = 0; }
+        return;
+    }
+    // exactly one digit d satisfies this (its bucket holds the k-th largest key)
+    if (picker && above < krem && krem <= above + mine) {
+        const int word = pass >> 2, shift = 8 * (3 - (pass & 3));
+        st[3 + word] = (int32_t)((uint32_t)st[3 + word] | ((uint32_t)d << shift));
+        const int knew = krem - above;
+        st[0] = knew;
+        if (mine == knew || pass == 11) { st[1] = 1; st[2] = pass + 1; }
+    }
+}
+
 __global__ void topk_init(const int32_t* __restrict__ k, int nbatch, int32_t* __restrict__ state) {
     const int b = blockIdx.x;
     int32_t* st = state + (int64_t)b * TK_STRIDE;
     for (int i = threadIdx.x; i < TK_STRIDE; i += blockDim.x) st[i] = 0;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const int kk = k[b];
-        st[0] = kk;
-        if (kk <= 0) { st[1] = 1; st[2] = 13; }  // select nothing
-    }
+    if (threadIdx.x == 0) topk_state_init(st, k[b]);
 }
 
 __global__ __launch_bounds__(256) void topk_hist(const float* __restrict__ logits, int ld,
@@ -89,7 +132,7 @@ __global__ __launch_bounds__(256) void topk_hist(const float* __restrict__ logit
         if (st[1]) continue;
         const Key96 key = make_key(logits[i * ld], c);
         if (cmp_prefix(key, st, pass) != 0) continue;
-        const uint32_t digit = (key.w[pass >> 2] >> (8 * (3 - (pass & 3)))) & 0xFFu;
+        const uint32_t digit = key_digit(key, pass);
         if (use_lds && nbatch == 1) {
             // Occupancy logits of one frame share their sign and exponent: in the first passes nearly every row of a wave
             // falls into the same one or two bins, and 64 LDS atomics on one address serialise.  The lanes of a wave that
@@ -161,23 +204,26 @@ __global__ __launch_bounds__(1024) void topk_pick1_kernel(int pass, int32_t* __r
     __syncthreads();
     if (q == 0) h[d] = hq[0][d] + hq[1][d] + hq[2][d] + hq[3][d];
     __syncthreads();
-    const int krem = st[0];
-    int above = 0;
-    if (q == 0) {
-        for (int j = d + 1; j < 256; ++j) above += h[j];
-        if (d == 0) total_s = above + h[0];
-    }
-    __syncthreads();
-    if (q != 0) return;
-    if (pass == 0 && total_s <= krem) {
-        if (d == 0) { st[1] = 1; st[2] = 0; }      // no more than k rows: keep them all
-        return;
-    }
-    if (above < krem && krem <= above + h[d]) {
-        st[3] = (int32_t)((uint32_t)st[3] | ((uint32_t)d << (8 * (3 - pass))));
-        const int knew = krem - above;
-        st[0] = knew;
-        if (h[d] == knew) { st[1] = 1; st[2] = pass + 1; }
+    topk_pick_step(h, st, pass, d, q == 0, &total_s);
+}
+
+// Passes [first, last) of ONE item's radix select in one 1024-thread workgroup, the state words `st` in LDS: per pass zero the
+// bins, histogram the rows that match the prefix, pick.  row_key(i, pass, key): row i's key, or false for a row that cannot count.
+template <class I, class RowKey>
+__device__ __forceinline__ void topk_rounds(int first, int last, I n, int32_t* st, int* h, int* total_s, RowKey row_key) {
+    const int t = threadIdx.x;
+    for (int pass = first; pass < last; ++pass) {
+        if (st[1]) break;                              // uniform: st is only written between barriers
+        if (t < 256) h[t] = 0;
+        __syncthreads();
+        for (I i = t; i < n; i += 1024) {
+            Key96 key;
+            if (!row_key(i, pass, key) || cmp_prefix(key, st, pass) != 0) continue;
+            atomicAdd(&h[key_digit(key, pass)], 1);
+        }
+        __syncthreads();
+        topk_pick_step(h, st, pass, t, t < 256, total_s);
+        __syncthreads();
     }
 }
 
@@ -188,40 +234,19 @@ __global__ __launch_bounds__(1024) void topk_tail_kernel(const float* __restrict
                                                          int64_t n, int32_t* __restrict__ state) {
     __shared__ int32_t st[8];
     __shared__ int h[256];
+    __shared__ int total_s;
     const int t = threadIdx.x;
     if (state[1] != 0) return;
     if (t < 8) st[t] = state[t];
     __syncthreads();
-    for (int pass = 4; pass < 12; ++pass) {
-        if (st[1]) break;                              // uniform: st is only written between barriers
-        if (t < 256) h[t] = 0;
-        __syncthreads();
-        for (int64_t i = t; i < n; i += 1024) {
-            // the logit alone decides for almost every row: the coordinates are read for the rows on the boundary only
-            if (float_key(logits[i * ld]) != (uint32_t)st[3]) continue;
-            const int4 c = reinterpret_cast<const int4*>(coords)[i];
-            if (c.x != 0) continue;
-            const Key96 key = make_key(logits[i * ld], c);
-            if (cmp_prefix(key, st, pass) != 0) continue;
-            atomicAdd(&h[(key.w[pass >> 2] >> (8 * (3 - (pass & 3)))) & 0xFFu], 1);
-        }
-        __syncthreads();
-        const int krem = st[0];
-        int above = 0, mine = 0;
-        if (t < 256) {
-            mine = h[t];
-            for (int j = t + 1; j < 256; ++j) above += h[j];
-        }
-        __syncthreads();
-        if (t < 256 && above < krem && krem <= above + mine) {
-            const int word = pass >> 2, shift = 8 * (3 - (pass & 3));
-            st[3 + word] = (int32_t)((uint32_t)st[3 + word] | ((uint32_t)t << shift));
-            const int knew = krem - above;
-            st[0] = knew;
-            if (mine == knew || pass == 11) { st[1] = 1; st[2] = pass + 1; }
-        }
-        __syncthreads();
-    }
+    topk_rounds(4, 12, n, st, h, &total_s, [&](int64_t i, int, Key96& key) {
+        // the logit alone decides for almost every row: the coordinates are read for the rows on the boundary only
+        if (float_key(logits[i * ld]) != (uint32_t)st[3]) return false;
+        const int4 c = reinterpret_cast<const int4*>(coords)[i];
+        if (c.x != 0) return false;
+        key = make_key(logits[i * ld], c);
+        return true;
+    });
     if (t < 8) state[t] = st[t];
 }
 
@@ -231,29 +256,12 @@ __global__ __launch_bounds__(256) void topk_pick(int pass, int32_t* __restrict__
     int32_t* st = state + (int64_t)blockIdx.x * TK_STRIDE;
     const int d = threadIdx.x;
     h[d] = st[8 + d];
-    __syncthreads();
-    // every thread reads the batch state before anyone rewrites it (writes come after the barrier)
+    st[8 + d] = 0;                 // the bins are clear for the next pass's histogram
+    // every thread reads the batch state before anyone rewrites it (the step's writes come after its barrier)
     const int done = st[1];
-    const int krem = st[0];
-    int above = 0;
-    for (int j = d + 1; j < 256; ++j) above += h[j];
-    if (d == 0) total_s = above + h[0];
     __syncthreads();
-    st[8 + d] = 0;
-    if (done) return;
-    if (pass == 0 && total_s <= krem) {
-        // the batch has no more than k rows: keep them all (compare zero prefix bytes)
-        if (d == 0) { st[1] = 1; st[2] = 0; }
-        return;
-    }
-    // exactly one digit d satisfies this (its bucket holds the k-th largest key)
-    if (above < krem && krem <= above + h[d]) {
-        const int word = pass >> 2, shift = 8 * (3 - (pass & 3));
-        st[3 + word] = (int32_t)((uint32_t)st[3 + word] | ((uint32_t)d << shift));
-        const int knew = krem - above;
-        st[0] = knew;
-        if (h[d] == knew || pass == 11) { st[1] = 1; st[2] = pass + 1; }
-    }
+    if (done) return;              // uniform
+    topk_pick_step(h, st, pass, d, true, &total_s);
 }
 
 __global__ __launch_bounds__(256) void topk_write_mask(const float* __restrict__ logits, int ld,
@@ -285,45 +293,15 @@ __global__ __launch_bounds__(1024) void topk_small_kernel(const float* __restric
     const int t = threadIdx.x;
     if (t < 8) st[t] = 0;
     __syncthreads();
-    if (t == 0) {
-        const int kk = k[0];
-        st[0] = kk;
-        if (kk <= 0) { st[1] = 1; st[2] = 13; }       // select nothing
-    }
+    if (t == 0) topk_state_init(st, k[0]);
     __syncthreads();
-    for (int pass = 0; pass < 12; ++pass) {
-        if (st[1]) break;                              // uniform: st is only written between barriers
-        if (t < 256) h[t] = 0;
-        __syncthreads();
-        const bool logit_only = pass < 4;              // a pass over the logit bytes: the tie-break key is not needed
-        for (int i = t; i < n; i += 1024) {
-            const int4 c = logit_only ? make_int4(0, 0, 0, 0) : reinterpret_cast<const int4*>(coords)[i];
-            if (c.x != 0) continue;
-            const Key96 key = make_key(logits[(int64_t)i * ld], c);
-            if (cmp_prefix(key, st, pass) != 0) continue;
-            atomicAdd(&h[(key.w[pass >> 2] >> (8 * (3 - (pass & 3)))) & 0xFFu], 1);
-        }
-        __syncthreads();
-        // topk_pick on the LDS state: every thread reads before anyone writes
-        const int krem = st[0];
-        int above = 0, mine = 0;
-        if (t < 256) {
-            mine = h[t];
-            for (int j = t + 1; j < 256; ++j) above += h[j];
-            if (t == 0) total_s = above + mine;
-        }
-        __syncthreads();
-        if (pass == 0 && total_s <= krem) {
-            if (t == 0) { st[1] = 1; st[2] = 0; }      // no more than k rows: keep them all
-        } else if (t < 256 && above < krem && krem <= above + mine) {
-            const int word = pass >> 2, shift = 8 * (3 - (pass & 3));
-            st[3 + word] = (int32_t)((uint32_t)st[3 + word] | ((uint32_t)t << shift));
-            const int knew = krem - above;
-            st[0] = knew;
-            if (mine == knew || pass == 11) { st[1] = 1; st[2] = pass + 1; }
-        }
-        __syncthreads();
-    }
+    topk_rounds(0, 12, n, st, h, &total_s, [&](int i, int pass, Key96& key) {
+        // a pass over the logit bytes: the tie-break key is not needed
+        const int4 c = pass < 4 ? make_int4(0, 0, 0, 0) : reinterpret_cast<const int4*>(coords)[i];
+        if (c.x != 0) return false;
+        key = make_key(logits[(int64_t)i * ld], c);
+        return true;
+    });
     const int nb = st[2];
     for (int i = t; i < n; i += 1024) {
         const int4 c = reinterpret_cast<const int4*>(coords)[i];
@@ -332,14 +310,6 @@ __global__ __launch_bounds__(1024) void topk_small_kernel(const float* __restric
         mask[i] = m;
     }
     for (int i = t; i < TK_STRIDE; i += 1024) state[i] = i < 8 ? st[i] : 0;      // as the separate launches leave it
-}
-
-__global__ __launch_bounds__(256) void coords_to_keys(const int32_t* __restrict__ coords, int64_t n,
-                                                      uint64_t* __restrict__ keys) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int4 c = reinterpret_cast<const int4*>(coords)[i];
-    keys[i] = pack_key(c.x, c.y, c.z, c.w);
 }
 
 // ---- execution order of a kernel map's output rows -------------------------------------------
@@ -424,45 +394,29 @@ __global__ __launch_bounds__(256) void order_keys64_kernel(const uint32_t* __res
     keys[i] = key;
 }
 
+// the OR of `m` over each aligned run of 32 lanes, in every lane of the run (the lanes of a wave hold consecutive positions)
+__device__ __forceinline__ uint32_t tile_or_mask(uint32_t m) {
+#pragma unroll
+    for (int d = 1; d < 32; d <<= 1) m |= __shfl_xor(m, d, 64);
+    return m;
+}
+
 // One OR-mask per 32 execution positions (the offsets a 32-row MFMA tile has to execute).  The neighbour table itself stays
 // in output-row order: the convolution kernels read row order[pos] of it (csrc/conv.hip) — until round 4 this kernel also
 // wrote a second, permuted copy of the table (557 MB on the 5.16 M-row candidate set of a config-2 frame, read once).
 __global__ __launch_bounds__(256) void group_masks_kernel(const int32_t* __restrict__ order, const uint32_t* __restrict__ row_mask,
                                                           int64_t n, uint32_t* __restrict__ group_mask32) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    uint32_t m = (i < n) ? row_mask[order[i]] : 0u;
-#pragma unroll
-    for (int d = 1; d < 32; d <<= 1) m |= __shfl_xor(m, d, 64);
+    const uint32_t m = tile_or_mask((i < n) ? row_mask[order[i]] : 0u);
     if (i < n && (threadIdx.x & 31) == 0) group_mask32[i >> 5] = m;
 }
 
-// out[pos] = table[order[pos]] (rows of K ints): the permuted copy of a neighbour table that the weight-gradient kernels of
-// the training path index by execution position (csrc/conv_bwd.hip).  A block owns 256 consecutive positions; the rows are
-// contiguous in the source and the destination is written fully coalesced.
-__global__ __launch_bounds__(256) void permute_rows_kernel(const int32_t* __restrict__ order, const int32_t* __restrict__ nbr,
-                                                           int64_t n, int K, int32_t* __restrict__ nbr_sorted) {
-    __shared__ int32_t src_row[256];
-    const int64_t r0 = (int64_t)blockIdx.x * 256;
-    const int64_t i = r0 + threadIdx.x;
-    src_row[threadIdx.x] = (i < n) ? order[i] : 0;
-    __syncthreads();
-    const int rows = (int)((n - r0 < 256) ? (n - r0) : 256);
-    const int total = rows * K;
-    int32_t* dst = nbr_sorted + r0 * K;
-    for (int e = threadIdx.x; e < total; e += 256) {
-        const int lr = e / K;
-        const int k = e - lr * K;
-        dst[e] = nbr[(int64_t)src_row[lr] * K + k];
-    }
-}
-
-
 // Offset counts, keys and the whole sort of a map of at most RS_SMALL_N (16,384) rows in ONE workgroup: what the ordering of
 // such a map ran as a memset and three launches (mask_bit_counts_kernel, order_keys32_kernel, radix_sort_small_kernel),
-// each a few microseconds of work behind its dispatch.  Same counts, same key, same sort: the same order.
-template <int ROUNDS>
-__global__ __launch_bounds__(RS_SMALL_THREADS) void order_small_kernel(const uint32_t* __restrict__ row_mask, int n, uint32_t* keys_a,
-                                                                      uint32_t* keys_b, int32_t* va, int32_t* vb) {
+// each a few microseconds of work behind its dispatch.  Same counts, same key, same sort: the same order.  mask_of(i): the
+// neighbour mask of row i.  The sorted rows (from an iota) end in `order`.  Every thread of the workgroup calls it.
+template <int ROUNDS, class MaskOf>
+__device__ __forceinline__ void order_small_body(MaskOf mask_of, int n, uint32_t* keys_a, uint32_t* keys_b, int32_t* vals, int32_t* order) {
     __shared__ unsigned cnt27[27];
     __shared__ int pos_s[27];
     const int t = threadIdx.x;
@@ -472,7 +426,7 @@ __global__ __launch_bounds__(RS_SMALL_THREADS) void order_small_kernel(const uin
 #pragma unroll
     for (int b = 0; b < 27; ++b) mine[b] = 0u;
     for (int i = t; i < n; i += RS_SMALL_THREADS) {
-        const uint32_t m = row_mask[i];
+        const uint32_t m = mask_of(i);
 #pragma unroll
         for (int b = 0; b < 27; ++b) mine[b] += (m >> b) & 1u;
     }
@@ -485,9 +439,15 @@ __global__ __launch_bounds__(RS_SMALL_THREADS) void order_small_kernel(const uin
     }
     __syncthreads();
     order_bit_positions(cnt27, pos_s);
-    for (int i = t; i < n; i += RS_SMALL_THREADS) keys_a[i] = order_key_of(row_mask[i] & 0x7FFFFFFu, pos_s);
+    for (int i = t; i < n; i += RS_SMALL_THREADS) keys_a[i] = order_key_of(mask_of(i) & 0x7FFFFFFu, pos_s);
     __syncthreads();
-    radix_sort_small_body<uint32_t, ROUNDS, 9>(keys_a, keys_b, va, vb, 1, n, 0, 27, 3);      // 27 bits = three 9-bit passes: the result ends in the b-side
+    radix_sort_small_body<uint32_t, ROUNDS, 9>(keys_a, keys_b, vals, order, 1, n, 0, 27, 3);      // 27 bits = three 9-bit passes: the result ends in the b-side
+}
+
+template <int ROUNDS>
+__global__ __launch_bounds__(RS_SMALL_THREADS) void order_small_kernel(const uint32_t* __restrict__ row_mask, int n, uint32_t* keys_a,
+                                                                      uint32_t* keys_b, int32_t* va, int32_t* vb) {
+    order_small_body<ROUNDS>([&](int i) { return row_mask[i]; }, n, keys_a, keys_b, va, vb);
 }
 
 // ---- a small kernel map and its execution order in ONE launch -----------------------------------------------------------
@@ -499,10 +459,11 @@ __global__ __launch_bounds__(RS_SMALL_THREADS) void order_small_kernel(const uin
 // against 36, 512 rows 66 against 46 — and 433 against 77 at 4,096: the probes (27 per row, ~150 vector instructions
 // each) are then ONE CU's work, 360 of the 433 us; hence the 256-row limit.
 constexpr int SMALL_MAP_MAX = 256;
+static_assert(rs_small_rounds(SMALL_MAP_MAX) == 1, "small_map_kernel sorts with the 1-round body: one round of 64 keys per wave");
 
 // (kernel size as a template parameter: with a runtime K the index arithmetic of a probe — e / K, k % ks, three modulos by the
 // parent pitch — is ~250 vector instructions, and ONE CU issues all of them: 190 us of a 4,096-row map)
-template <int ROUNDS, int KS>
+template <int KS>
 __global__ __launch_bounds__(RS_SMALL_THREADS) void small_map_kernel(const int32_t* __restrict__ out_coords, int n,
                                                                     const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals,
                                                                     uint64_t tmask, int tshift, int step, int pitch,
@@ -511,13 +472,10 @@ __global__ __launch_bounds__(RS_SMALL_THREADS) void small_map_kernel(const int32
                                                                     int32_t* vals_x) {
     constexpr int ks = KS, K = KS * KS * KS;
     __shared__ unsigned rm[SMALL_MAP_MAX];
-    __shared__ unsigned cnt27[27];
-    __shared__ int pos_s[27];
     const int t = threadIdx.x;
     const bool pow2 = pitch > 0 && (pitch & (pitch - 1)) == 0;
     auto off_grid = [&](int v) { return pow2 ? (v & (pitch - 1)) != 0 : (v % pitch) != 0; };
     for (int i = t; i < n; i += RS_SMALL_THREADS) rm[i] = 0u;
-    if (t < 27) cnt27[t] = 0u;
     __syncthreads();
     // probes, (row, offset) pairs offset-fastest like kernel_map_kernel — eight per thread at a time: one workgroup has
     // 16 waves to hide the table's load latency with, so the loads of a batch are issued together (first slot of every
@@ -559,86 +517,79 @@ __global__ __launch_bounds__(RS_SMALL_THREADS) void small_map_kernel(const int32
         }
     }
     __syncthreads();
-    // row masks out; rows per offset
-    unsigned mine[27];
-#pragma unroll
-    for (int b = 0; b < 27; ++b) mine[b] = 0u;
-    for (int i = t; i < n; i += RS_SMALL_THREADS) {
-        const uint32_t m = rm[i];
-        row_mask[i] = m;
-#pragma unroll
-        for (int b = 0; b < 27; ++b) mine[b] += (m >> b) & 1u;
-    }
-#pragma unroll
-    for (int b = 0; b < 27; ++b) {
-        unsigned v = mine[b];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-        if ((t & 63) == 0 && v) atomicAdd(&cnt27[b], v);
-    }
-    __syncthreads();
-    order_bit_positions(cnt27, pos_s);
-    for (int i = t; i < n; i += RS_SMALL_THREADS) keys_a[i] = order_key_of(rm[i] & 0x7FFFFFFu, pos_s);
-    __syncthreads();
-    // 27 key bits = three 9-bit passes: the sorted values (the rows, from an iota) end in the b-side = `order`
-    radix_sort_small_body<uint32_t, ROUNDS, 9>(keys_a, keys_b, vals_x, order, 1, n, 0, 27, 3);
-    // group masks (positions are consecutive across a wave's lanes)
+    // row masks out; the order from the masks in LDS (one round: SMALL_MAP_MAX); group masks
+    for (int i = t; i < n; i += RS_SMALL_THREADS) row_mask[i] = rm[i];
+    order_small_body<1>([&](int i) { return rm[i]; }, n, keys_a, keys_b, vals_x, order);
     for (int i0 = 0; i0 < n; i0 += RS_SMALL_THREADS) {
         const int i = i0 + t;
-        uint32_t m = (i < n) ? rm[order[i]] : 0u;
-#pragma unroll
-        for (int d = 1; d < 32; d <<= 1) m |= __shfl_xor(m, d, 64);
+        const uint32_t m = tile_or_mask((i < n) ? rm[order[i]] : 0u);
         if (i < n && (t & 31) == 0) group_mask32[i >> 5] = m;
     }
+}
+
+// out[pos] = table[order[pos]] (rows of K ints): the permuted copy of a neighbour table that the weight-gradient kernels of
+// the training path index by execution position (csrc/conv_bwd.hip).  A block owns 256 consecutive positions; the rows are
+// contiguous in the source and the destination is written fully coalesced.
+__global__ __launch_bounds__(256) void permute_rows_kernel(const int32_t* __restrict__ order, const int32_t* __restrict__ nbr,
+                                                           int64_t n, int K, int32_t* __restrict__ nbr_sorted) {
+    __shared__ int32_t src_row[256];
+    const int64_t r0 = (int64_t)blockIdx.x * 256;
+    const int64_t i = r0 + threadIdx.x;
+    src_row[threadIdx.x] = (i < n) ? order[i] : 0;
+    __syncthreads();
+    const int rows = (int)((n - r0 < 256) ? (n - r0) : 256);
+    const int total = rows * K;
+    int32_t* dst = nbr_sorted + r0 * K;
+    for (int e = threadIdx.x; e < total; e += 256) {
+        const int lr = e / K;
+        const int k = e - lr * K;
+        dst[e] = nbr[(int64_t)src_row[lr] * K + k];
+    }
+}
+
+__global__ __launch_bounds__(256) void coords_to_keys(const int32_t* __restrict__ coords, int64_t n,
+                                                      uint64_t* __restrict__ keys) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int4 c = reinterpret_cast<const int4*>(coords)[i];
+    keys[i] = pack_key(c.x, c.y, c.z, c.w);
 }
 
 }  // namespace pcc
 
 using namespace pcc;
 
-extern "C" {
-
-int64_t pcc_small_map_max(void) {
-    static int off = -1;          // PCC_SMALL_MAP=0: always the separate launches (A/B)
-    if (off < 0) { const char* e = getenv("PCC_SMALL_MAP"); off = (e && e[0] == '0') ? 1 : 0; }
-    return off ? 0 : SMALL_MAP_MAX;
+extern "C" int64_t pcc_sort_scratch_bytes(int64_t n) {
+    if (n < 1) n = 1;
+    return 2 * align256(n * 8) + align256(n * 4) + radix_sort_counter_bytes(n) + 256;
 }
 
-int pcc_small_kernel_map(const int32_t* out_coords, int64_t n_out, const uint64_t* in_keys, const int32_t* in_vals, int64_t in_cap,
-                         int32_t ksize, int32_t step, int32_t sign, int32_t* nbr, uint32_t* row_mask, int32_t* order,
-                         uint32_t* group_mask32, void* scratch, int64_t scratch_bytes, void* stream) {
-    PCC_REQUIRE(ksize == 2 || ksize == 3, "pcc_small_kernel_map: kernel size must be 2 or 3");
-    PCC_REQUIRE(sign == 1 || sign == -1, "pcc_small_kernel_map: sign must be +1/-1");
-    PCC_REQUIRE(in_cap > 0 && (in_cap & (in_cap - 1)) == 0, "pcc_small_kernel_map: bad capacity");
-    PCC_REQUIRE(step >= 1, "pcc_small_kernel_map: step must be >= 1");
-    PCC_REQUIRE(n_out >= 0 && n_out <= SMALL_MAP_MAX, "pcc_small_kernel_map: %lld rows exceed %d", (long long)n_out, SMALL_MAP_MAX);
-    PCC_REQUIRE(scratch_bytes >= pcc_sort_scratch_bytes(n_out), "pcc_small_kernel_map: scratch too small");
-    if (n_out <= 0) return PCC_OK;
-    const int in_stride = sign > 0 ? step : 2 * step;
-    const int pitch = sign > 0 ? 0 : 2 * step;
+namespace {
+
+// the layout of those bytes: what pcc_sort_coords, pcc_order_rows_by_mask and pcc_small_kernel_map carve out of their scratch
+struct SortScratch {
+    void* keys_a;          // n keys of up to 64 bits, ping
+    void* keys_b;          // pong
+    int32_t* vals_x;       // n values: the side of the value ping-pong that is not the caller's output
+    void* counters;        // radix_sort_counter_bytes(n)
+    uint32_t* tail;        // the last 256 bytes: the execution order keeps its 27 offset counts here
+};
+
+SortScratch carve_sort_scratch(void* scratch, int64_t n) {
+    if (n < 1) n = 1;
     char* p = reinterpret_cast<char*>(scratch);
-    uint32_t* keys_a = reinterpret_cast<uint32_t*>(p); p += align256(n_out * 8);
-    uint32_t* keys_b = reinterpret_cast<uint32_t*>(p); p += align256(n_out * 8);
-    int32_t* vals_x = reinterpret_cast<int32_t*>(p);
-    const int rounds = (int)(((n_out + RS_SMALL_WAVES - 1) / RS_SMALL_WAVES + 63) / 64);
-    hipStream_t st = as_stream(stream);
-#define PCC_SMALL_MAP(R, S)                                                                                                          \
-    hipLaunchKernelGGL((small_map_kernel<R, S>), dim3(1), dim3(RS_SMALL_THREADS), 0, st, out_coords, (int)n_out, in_keys, in_vals,    \
-                       (uint64_t)(in_cap - 1), grid_shift_of(in_stride), sign * step, pitch, nbr, row_mask, order,                   \
-                       group_mask32, keys_a, keys_b, vals_x)
-#define PCC_SMALL_MAP_R(S)                                                                                                           \
-    do {                                                                                                                             \
-        if (rounds <= 1) PCC_SMALL_MAP(1, S);                                                                                        \
-        else if (rounds <= 2) PCC_SMALL_MAP(2, S);                                                                                   \
-        else PCC_SMALL_MAP(4, S);                                                                                                    \
-    } while (0)
-    if (ksize == 3) PCC_SMALL_MAP_R(3);
-    else PCC_SMALL_MAP_R(2);
-#undef PCC_SMALL_MAP_R
-#undef PCC_SMALL_MAP
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    SortScratch s;
+    s.keys_a = p; p += align256(n * 8);
+    s.keys_b = p; p += align256(n * 8);
+    s.vals_x = reinterpret_cast<int32_t*>(p); p += align256(n * 4);
+    s.counters = p; p += radix_sort_counter_bytes(n);
+    s.tail = reinterpret_cast<uint32_t*>(p);
+    return s;
 }
+
+}  // namespace
+
+extern "C" {
 
 int64_t pcc_topk_state_elems(int32_t nbatch) { return (int64_t)nbatch * TK_STRIDE + (nbatch == 1 ? (int64_t)TK1_GROUPS * 256 : 0); }
 
@@ -693,50 +644,67 @@ int pcc_order_rows_by_mask(const uint32_t* row_mask, const int32_t* coords, int6
     PCC_REQUIRE(tensor_stride >= 1, "pcc_order_rows_by_mask: bad tensor stride");
     PCC_REQUIRE(scratch_bytes >= pcc_sort_scratch_bytes(n), "pcc_order_rows_by_mask: scratch too small");
     hipStream_t st = as_stream(stream);
-    char* p = reinterpret_cast<char*>(scratch);
-    char* keys_a = p; p += align256(n * 8);
-    char* keys_b = p; p += align256(n * 8);
-    int32_t* vals_x = reinterpret_cast<int32_t*>(p); p += align256(n * 4);
-    void* counters = p;
-    uint32_t* bit_counts = reinterpret_cast<uint32_t*>(p + radix_sort_counter_bytes(n));       // 27 words in the scratch's 256-byte tail
+    const SortScratch s = carve_sort_scratch(scratch, n);
     if (small_path_enabled(0) && block_log2 < 0 && n <= RS_SMALL_N) {      // PCC_ORDER_SMALL=0: never (A/B)
         // counts + keys + sort in one workgroup (27 key bits = three 9-bit passes: the sorted rows end in the b-side = `order`)
-        const int rounds = (int)(((n + RS_SMALL_WAVES - 1) / RS_SMALL_WAVES + 63) / 64);
-        uint32_t* ka = reinterpret_cast<uint32_t*>(keys_a);
-        uint32_t* kb = reinterpret_cast<uint32_t*>(keys_b);
-#define PCC_ORDER_SMALL(R) hipLaunchKernelGGL(order_small_kernel<R>, dim3(1), dim3(RS_SMALL_THREADS), 0, st, row_mask, (int)n, ka, kb, vals_x, order)
-        if (rounds <= 1) PCC_ORDER_SMALL(1);
-        else if (rounds <= 2) PCC_ORDER_SMALL(2);
-        else if (rounds <= 4) PCC_ORDER_SMALL(4);
-        else if (rounds <= 8) PCC_ORDER_SMALL(8);
-        else PCC_ORDER_SMALL(16);
-#undef PCC_ORDER_SMALL
-        hipLaunchKernelGGL(group_masks_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, order, row_mask, n, group_mask32);
-        PCC_LAUNCH_CHECK();
-        return PCC_OK;
-    }
-    PCC_CHECK_HIP(hipMemsetAsync(bit_counts, 0, 27 * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(mask_bit_counts_kernel, dim3(blocks_for(n, 256 * 16, 512)), dim3(256), 0, st, row_mask, n, bit_counts);
-    const int begin = 0, end = block_log2 >= 0 ? 64 : 27;
-    const int digit_bits = block_log2 >= 0 ? 8 : radix_sort_order_digit_bits(n);      // 27 bits: three 9-bit passes instead of four 8-bit ones
-    // the sorted values must land in `order`: they end in the b-side when the pass count is odd
-    const bool in_b = radix_sort_result_in_b(begin, end, digit_bits);
-    int32_t* va = in_b ? vals_x : order;
-    int32_t* vb = in_b ? order : vals_x;
-    int rc;
-    if (block_log2 < 0) {
-        hipLaunchKernelGGL(order_keys32_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, row_mask, n, bit_counts,
-                           reinterpret_cast<uint32_t*>(keys_a));
-        rc = radix_sort_pairs_u32(reinterpret_cast<uint32_t*>(keys_a), reinterpret_cast<uint32_t*>(keys_b), va, vb, true, n, begin, end,
-                                  counters, st, digit_bits);
+        rs_small_dispatch(rs_small_rounds((int)n), [&](auto r) {
+            hipLaunchKernelGGL(order_small_kernel<decltype(r)::value>, dim3(1), dim3(RS_SMALL_THREADS), 0, st, row_mask, (int)n,
+                               static_cast<uint32_t*>(s.keys_a), static_cast<uint32_t*>(s.keys_b), s.vals_x, order);
+        });
     } else {
-        hipLaunchKernelGGL(order_keys64_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, row_mask, coords, n, block_log2, tensor_stride,
-                           bit_counts, reinterpret_cast<uint64_t*>(keys_a));
-        rc = radix_sort_pairs_u64(reinterpret_cast<uint64_t*>(keys_a), reinterpret_cast<uint64_t*>(keys_b), va, vb, true, n, begin, end,
-                                  counters, st);
+        uint32_t* bit_counts = s.tail;
+        PCC_CHECK_HIP(hipMemsetAsync(bit_counts, 0, 27 * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(mask_bit_counts_kernel, dim3(blocks_for(n, 256 * 16, 512)), dim3(256), 0, st, row_mask, n, bit_counts);
+        const int begin = 0, end = block_log2 >= 0 ? 64 : 27;
+        const int digit_bits = block_log2 >= 0 ? 8 : radix_sort_order_digit_bits(n);      // 27 bits: three 9-bit passes instead of four 8-bit ones
+        // the sorted values must land in `order`: they end in the b-side when the pass count is odd
+        const bool in_b = radix_sort_result_in_b(begin, end, digit_bits);
+        int32_t* va = in_b ? s.vals_x : order;
+        int32_t* vb = in_b ? order : s.vals_x;
+        int rc;
+        if (block_log2 < 0) {
+            uint32_t* ka = static_cast<uint32_t*>(s.keys_a);
+            hipLaunchKernelGGL(order_keys32_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, row_mask, n, bit_counts, ka);
+            rc = radix_sort_pairs_u32(ka, static_cast<uint32_t*>(s.keys_b), va, vb, true, n, begin, end, s.counters, st, digit_bits);
+        } else {
+            uint64_t* ka = static_cast<uint64_t*>(s.keys_a);
+            hipLaunchKernelGGL(order_keys64_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, row_mask, coords, n, block_log2, tensor_stride,
+                               bit_counts, ka);
+            rc = radix_sort_pairs_u64(ka, static_cast<uint64_t*>(s.keys_b), va, vb, true, n, begin, end, s.counters, st);
+        }
+        if (rc) return rc;
     }
-    if (rc) return rc;
     hipLaunchKernelGGL(group_masks_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, order, row_mask, n, group_mask32);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+int64_t pcc_small_map_max(void) {
+    static int off = -1;          // PCC_SMALL_MAP=0: always the separate launches (A/B)
+    if (off < 0) { const char* e = getenv("PCC_SMALL_MAP"); off = (e && e[0] == '0') ? 1 : 0; }
+    return off ? 0 : SMALL_MAP_MAX;
+}
+
+int pcc_small_kernel_map(const int32_t* out_coords, int64_t n_out, const uint64_t* in_keys, const int32_t* in_vals, int64_t in_cap,
+                         int32_t ksize, int32_t step, int32_t sign, int32_t* nbr, uint32_t* row_mask, int32_t* order,
+                         uint32_t* group_mask32, void* scratch, int64_t scratch_bytes, void* stream) {
+    PCC_REQUIRE(ksize == 2 || ksize == 3, "pcc_small_kernel_map: kernel size must be 2 or 3");
+    PCC_REQUIRE(sign == 1 || sign == -1, "pcc_small_kernel_map: sign must be +1/-1");
+    PCC_REQUIRE(in_cap > 0 && (in_cap & (in_cap - 1)) == 0, "pcc_small_kernel_map: bad capacity");
+    PCC_REQUIRE(step >= 1, "pcc_small_kernel_map: step must be >= 1");
+    PCC_REQUIRE(n_out >= 0 && n_out <= SMALL_MAP_MAX, "pcc_small_kernel_map: %lld rows exceed %d", (long long)n_out, SMALL_MAP_MAX);
+    PCC_REQUIRE(scratch_bytes >= pcc_sort_scratch_bytes(n_out), "pcc_small_kernel_map: scratch too small");
+    if (n_out <= 0) return PCC_OK;
+    const int in_stride = sign > 0 ? step : 2 * step;
+    const int pitch = sign > 0 ? 0 : 2 * step;
+    const SortScratch s = carve_sort_scratch(scratch, n_out);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(1), dim3(RS_SMALL_THREADS), 0, as_stream(stream), out_coords, (int)n_out, in_keys, in_vals,
+                           (uint64_t)(in_cap - 1), grid_shift_of(in_stride), sign * step, pitch, nbr, row_mask, order, group_mask32,
+                           static_cast<uint32_t*>(s.keys_a), static_cast<uint32_t*>(s.keys_b), s.vals_x);
+    };
+    if (ksize == 3) launch(small_map_kernel<3>);
+    else launch(small_map_kernel<2>);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
 }
@@ -750,24 +718,18 @@ int pcc_permute_map_rows(const int32_t* nbr, const int32_t* order, int64_t n, in
     return PCC_OK;
 }
 
-int64_t pcc_sort_scratch_bytes(int64_t n) {
-    if (n < 1) n = 1;
-    return 2 * align256(n * 8) + align256(n * 4) + radix_sort_counter_bytes(n) + 256;
-}
-
 int pcc_sort_coords(const int32_t* coords, int64_t n, int32_t* perm, void* scratch, int64_t scratch_bytes, void* stream) {
     if (n <= 0) return PCC_OK;
     PCC_REQUIRE(n < (1ll << 31), "pcc_sort_coords: too many rows");
     PCC_REQUIRE(scratch_bytes >= pcc_sort_scratch_bytes(n), "pcc_sort_coords: scratch too small");
     hipStream_t st = as_stream(stream);
-    char* p = reinterpret_cast<char*>(scratch);
-    uint64_t* keys_a = reinterpret_cast<uint64_t*>(p); p += align256(n * 8);
-    uint64_t* keys_b = reinterpret_cast<uint64_t*>(p); p += align256(n * 8);
-    int32_t* vals_x = reinterpret_cast<int32_t*>(p); p += align256(n * 4);
-    void* counters = p;
+    const SortScratch s = carve_sort_scratch(scratch, n);
+    uint64_t* keys_a = static_cast<uint64_t*>(s.keys_a);
     hipLaunchKernelGGL(coords_to_keys, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, keys_a);
     const bool in_b = radix_sort_result_in_b(0, 64);
-    return radix_sort_pairs_u64(keys_a, keys_b, in_b ? vals_x : perm, in_b ? perm : vals_x, true, n, 0, 64, counters, st);
+    return radix_sort_pairs_u64(keys_a, static_cast<uint64_t*>(s.keys_b), in_b ? s.vals_x : perm, in_b ? perm : s.vals_x, true, n, 0, 64,
+                                s.counters, st);
 }
 
 }  // extern "C"
+

@@ -231,16 +231,10 @@ static int radix_sort_pairs(K* ka, K* kb, int32_t* va, int32_t* vb, bool iota, i
     PCC_REQUIRE(n < (1ll << 31), "radix sort: too many keys (%lld)", (long long)n);
     if (n <= 0) return PCC_OK;
     if (n <= RS_SMALL_N) {
-        const int rounds = (int)(((n + RS_SMALL_WAVES - 1) / RS_SMALL_WAVES + 63) / 64);
-#define PCC_RS_SMALL(R)                                                                                                             \
-    hipLaunchKernelGGL((radix_sort_small_kernel<K, R, DB>), dim3(1), dim3(RS_SMALL_THREADS), 0, st, ka, kb, va, vb, iota ? 1 : 0, (int)n, \
-                       begin_bit, end_bit, passes)
-        if (rounds <= 1) PCC_RS_SMALL(1);
-        else if (rounds <= 2) PCC_RS_SMALL(2);
-        else if (rounds <= 4) PCC_RS_SMALL(4);
-        else if (rounds <= 8) PCC_RS_SMALL(8);
-        else PCC_RS_SMALL(16);
-#undef PCC_RS_SMALL
+        rs_small_dispatch(rs_small_rounds((int)n), [&](auto r) {
+            hipLaunchKernelGGL((radix_sort_small_kernel<K, decltype(r)::value, DB>), dim3(1), dim3(RS_SMALL_THREADS), 0, st, ka, kb, va, vb,
+                               iota ? 1 : 0, (int)n, begin_bit, end_bit, passes);
+        });
         PCC_LAUNCH_CHECK();
         return PCC_OK;
     }

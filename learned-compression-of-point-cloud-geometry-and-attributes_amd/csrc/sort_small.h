@@ -1,7 +1,10 @@
 // The one-workgroup radix sort (n <= RS_SMALL_N keys, 1024 threads, all passes in one launch) as a device function: the
-// body of radix_sort_small_kernel (sort.hip) and a phase of small_map_kernel (select.hip), which builds a small kernel
-// map and its execution order in a single launch.  Every thread of a RS_SMALL_THREADS-thread workgroup must call it.
+// body of radix_sort_small_kernel (sort.hip) and the last phase of order_small_body (select.hip), which orders a map's
+// rows in a single launch.  Every thread of a RS_SMALL_THREADS-thread workgroup must call it.  Its launches pick the
+// compile-time round count through rs_small_rounds / rs_small_dispatch.
 #pragma once
+#include <type_traits>
+
 #include "sort.h"
 
 namespace pcc {
@@ -10,6 +13,19 @@ constexpr int RS_SMALL_THREADS = 1024;
 constexpr int RS_SMALL_WAVES = RS_SMALL_THREADS / 64;
 constexpr int RS_SMALL_ROUNDS = 16;                                       // rounds of 64 keys per wave, held in registers
 constexpr int64_t RS_SMALL_N = (int64_t)RS_SMALL_WAVES * 64 * RS_SMALL_ROUNDS;   // 16384
+
+// rounds of 64 keys a wave's chunk of n <= RS_SMALL_N keys takes
+__host__ __device__ constexpr int rs_small_rounds(int n) { return ((n + RS_SMALL_WAVES - 1) / RS_SMALL_WAVES + 63) / 64; }
+
+// f(std::integral_constant<int, R>) for the smallest built instance (R = 1, 2, 4, 8, 16 rounds) that holds `rounds`
+template <class F>
+inline void rs_small_dispatch(int rounds, F&& f) {
+    if (rounds <= 1) f(std::integral_constant<int, 1>{});
+    else if (rounds <= 2) f(std::integral_constant<int, 2>{});
+    else if (rounds <= 4) f(std::integral_constant<int, 4>{});
+    else if (rounds <= 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, RS_SMALL_ROUNDS>{});
+}
 
 // lanes of this wave that are active and hold the same DB-bit digit as the calling lane
 template <int DB = 8>
@@ -45,7 +61,7 @@ __device__ __forceinline__ void radix_sort_small_body(K* ka, K* kb, int32_t* va,
     __shared__ int tot[ND];
     __shared__ int wsum[ND / 64];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int chunk = ((n + RS_SMALL_WAVES - 1) / RS_SMALL_WAVES + 63) / 64 * 64;      // <= 64 * ROUNDS
+    const int chunk = rs_small_rounds(n) * 64;                                         // <= 64 * ROUNDS
     const int lo = w * chunk < n ? w * chunk : n;
     const int hi = lo + chunk < n ? lo + chunk : n;
     const uint64_t lt = (1ull << lane) - 1ull;

@@ -16,12 +16,12 @@ from oracle.coords import float_key          # ONE key for the oracle (oracle/co
 __all__ = ["float_key", "reference_topk", "reference_compact"]
 
 # ---- the constants of the launch code the tables are built around (the table test checks the tables against THESE) ----------
-TK_SMALL_N = 32768                     # csrc/select.hip:278  TK_SMALL_N: one workgroup up to here (one item)
-TK_LDS_BATCHES = 16                    # csrc/select.hip:19   TK_LDS_BATCHES: LDS histogram up to here, global atomics above
-TK_GRID_ROWS = 512 * 256               # csrc/select.hip:659  blocks_for(n, 256, 512): topk_hist strides above this row count
-TK1_ROWS_PER_ITER = 256 * 1024 * 4     # csrc/select.hip:119-120,131  TK1_GROUPS x TK1_THREADS x 4 rows: topk_hist1_kernel loops above
+TK_SMALL_N = 32768                     # csrc/select.hip:286  TK_SMALL_N: one workgroup up to here (one item)
+TK_LDS_BATCHES = 16                    # csrc/select.hip:30   TK_LDS_BATCHES: LDS histogram up to here, global atomics above
+TK_GRID_ROWS = 512 * 256               # csrc/select.hip:610  blocks_for(n, 256, 512): topk_hist strides above this row count
+TK1_ROWS_PER_ITER = 256 * 1024 * 4     # csrc/select.hip:162-163,174  TK1_GROUPS x TK1_THREADS x 4 rows: topk_hist1_kernel loops above
 TOPK_SMALL_BIT = 2                     # include/pcc_hip.h:192  bit of pcc_small_paths that allows the one-item kernels
-BATCH_MAX = 1023                       # csrc/common.h:53     BATCH_LIMIT + 1 items (csrc/select.hip:647)
+BATCH_MAX = 1023                       # csrc/common.h:53     BATCH_LIMIT + 1 items (csrc/select.hip:598)
 SCAN_TILE = 1024                       # csrc/coords.hip:29-31  SCAN_BLOCK x SCAN_ITEMS flags per workgroup
 SCAN_SECOND_ROWS = 256 * SCAN_TILE     # csrc/coords.hip:82   scan_of_block_sums takes SCAN_BLOCK block sums per iteration
 ROW_GRID_ELEMS = 65536 * 256           # csrc/coords.hip:865,873,881  blocks_for(n * c, 256, 65536): the row movers stride above
@@ -199,7 +199,7 @@ GLOBAL_ITEMS, GLOBAL_ROWS = (17, 64, 1023), (5000, 140001)
 
 
 def topk_path(nbatch, n, small_paths):
-    """pcc_topk_mask's choice (csrc/select.hip:645-682), from the constants above"""
+    """pcc_topk_mask's choice (csrc/select.hip:596-633), from the constants above"""
     one_item_kernels = bool(small_paths & TOPK_SMALL_BIT) and nbatch == 1
     if one_item_kernels and 0 < n <= TK_SMALL_N:
         return "small"

@@ -494,12 +494,17 @@ def test_canonical_sort_all_sizes(pcc, n):
     assert (perm == oc.sort_order(c)).all()
 
 
-@pytest.mark.parametrize("n,K", [(5, 27), (257, 27), (16_385, 8), (98_500, 27), (600_003, 27)])
-def test_mask_order_is_the_stable_sort_of_the_keys(pcc, n, K):
+@pytest.mark.parametrize("n,K,block_log2", [
+    pytest.param(5, 27, -1, id="5-27"), pytest.param(257, 27, -1, id="257-27"), pytest.param(16_385, 8, -1, id="16385-8"),
+    pytest.param(98_500, 27, -1, id="98500-27"), pytest.param(600_003, 27, -1, id="600003-27"),
+    pytest.param(257, 27, 3, id="257-27-blk3"), pytest.param(16_385, 8, 3, id="16385-8-blk3")])
+def test_mask_order_is_the_stable_sort_of_the_keys(pcc, n, K, block_log2):
     """pcc_order_rows_by_mask on synthetic masks (few distinct values -> long runs of equal keys, the real
     distribution): `order` must be THE stable ascending sort of the rare-offsets-first key — ranks come from
     ballots and per-wave counters, never from atomics, so equal keys keep their row order — with the permuted
-    table and the 32-position OR-masks consistent with it"""
+    table and the 32-position OR-masks consistent with it.  With spatial blocks (block_log2 = 3, stride-2 coordinates
+    of three batch items; the sizes on either side of the one-workgroup sort limit) the block id goes on top of the key:
+    the 64-bit sort."""
     from pcc_amd._lib import ptr, check, stream
     L = pcc.lib()
     rng = np.random.default_rng(n + K)
@@ -513,9 +518,20 @@ def test_mask_order_is_the_stable_sort_of_the_keys(pcc, n, K):
     gm = torch.empty((n + 31) // 32, dtype=torch.int32, device=DEV)
     nbytes = L.pcc_order_scratch_bytes(n)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
-    check(L.pcc_order_rows_by_mask(ptr(d_mask), None, n, -1, 1, ptr(order), ptr(gm), ptr(scratch), nbytes, stream()))
-    check(L.pcc_permute_map_rows(ptr(d_nbr), ptr(order), n, K, ptr(nbr_s), stream()))      # the training path's permuted copy
     key = order_key(mask)
+    if block_log2 < 0:
+        check(L.pcc_order_rows_by_mask(ptr(d_mask), None, n, -1, 1, ptr(order), ptr(gm), ptr(scratch), nbytes, stream()))
+    else:
+        ts = 2
+        flat = np.random.default_rng([n, K, block_log2]).choice(3 * 81 ** 3, size=n, replace=False)      # distinct (b, x, y, z)
+        c = np.stack([flat // 81 ** 3, (flat // 81 ** 2) % 81 - 40, (flat // 81) % 81 - 40, flat % 81 - 40], axis=1)
+        c[:, 1:] *= ts                                           # multiples of the stride in [-80, 80]
+        d_c = dev(c.astype(np.int32))
+        check(L.pcc_order_rows_by_mask(ptr(d_mask), ptr(d_c), n, block_log2, ts, ptr(order), ptr(gm), ptr(scratch), nbytes, stream()))
+        bx, by, bz = ((((c[:, j] // ts + 512) >> block_log2) & 0x3FF).astype(np.uint64) for j in (1, 2, 3))
+        blk = ((c[:, 0] & 3).astype(np.uint64) << np.uint64(30)) | (bx << np.uint64(20)) | (by << np.uint64(10)) | bz
+        key = (blk << np.uint64(32)) | key.astype(np.uint64)
+    check(L.pcc_permute_map_rows(ptr(d_nbr), ptr(order), n, K, ptr(nbr_s), stream()))      # the training path's permuted copy
     want = np.argsort(key, kind="stable")
     got = order.cpu().numpy()
     assert (got == want).all()
