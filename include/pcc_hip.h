@@ -645,6 +645,44 @@ int pcc_rans_lanes_decode(const uint8_t* data_host, const uint8_t* data, int64_t
                           int64_t n, const void* tables, int32_t* out_symbols, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Code length on the device (DESIGN.md "Target-rate coding"; csrc/code_length.hip): what the
+ * range coder above spends on a symbol sequence under the coding tables, in exact integers,
+ * without a plane, a sort or a host step.
+ *
+ * cost: [n_tables, cdf_stride] int32 of Q16 bits, built on the HOST by
+ * pcc_code_length_tables_build from the tables the coder takes: slot v <= cdf_sizes[t] - 2 of
+ * table t holds round(65536 * (16 - log2(freq))), freq = the low 16 bits of cdf[v+1] - cdf[v]
+ * as the coder reads it, float64 arithmetic; slot cdf_sizes[t] - 2 is the escape symbol; a
+ * frequency of 0 (which the coder refuses) and the unused tail of a row hold -1.
+ *
+ * A symbol s under table t costs, with v = s - offsets[t] and maxv = cdf_sizes[t] - 2:
+ * cost[t][v] when 0 <= v < maxv, else cost[t][maxv] + 4 * 65536 * (nb + nb / 15 + 1) with nb the
+ * number of 4-bit nibbles of raw = -2v - 1 (v < 0) or 2 (v - maxv): every bypass put codes 4 bits.
+ *
+ * out: DEVICE int64 [c + 3], zeroed by the call: out[0 .. c-1] Q16 bits per channel, out[c] the
+ * coder operations (symbols + bypass puts), out[c+1] the escapes, out[c+2] flags: bit 1 = table
+ * index out of range (or a cdf_sizes entry outside 2 .. cdf_stride), bit 2 = a slot of frequency
+ * 0 was hit, as in the lane coder.  With a flag set the sums are unspecified; nothing is read
+ * out of bounds.  Sums are integer atomics: two runs agree bit for bit.  1 <= c <= 4096.
+ * ------------------------------------------------------------------------------------- */
+int pcc_code_length_tables_build(const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
+                                 int32_t n_tables, int32_t* out);
+/* y [N, C] under params [N, 2C]: the symbols and indexes of pcc_gc_encode_prep, never written.
+ * cost / cdf_sizes / offsets (DEVICE) hold one table per scale level (`levels` of them). */
+int pcc_gc_code_length(const float* y, const float* params, int64_t n, int32_t c,
+                       const float* scale_table, int32_t levels, const int32_t* cost,
+                       int32_t cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                       int64_t* out, void* stream);
+/* z [N, C]: the symbols of pcc_eb_quantize, table index = channel (c tables). */
+int pcc_eb_code_length(const float* z, int64_t n, int32_t c, const float* medians, const int32_t* cost,
+                       int32_t cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                       int64_t* out, void* stream);
+/* int32 planes [c, n] (channel-major, any column order: the sums do not depend on it). */
+int pcc_code_length_planes(const int32_t* symbols, const int32_t* indexes, int64_t n, int32_t c,
+                           const int32_t* cost, int32_t cdf_stride, const int32_t* cdf_sizes,
+                           const int32_t* offsets, int32_t n_tables, int64_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * RAHT, the region-adaptive hierarchical transform (de Queiroz & Chou 2016): the attribute
  * transform of the octree + RAHT anchor codec (DESIGN.md "Anchor codec").  csrc/raht.hip.
  *

@@ -22,6 +22,6 @@ from .entropy_models import MeanScaleHyperprior, MeanScaleHyperprior_Map  # noqa
 from .model import ColorModel  # noqa: F401
 from .normals import estimate_normals  # noqa: F401
 from .voxelize import voxelize, downsample, Voxelized  # noqa: F401
-from . import synthetic, utils, parallel, render, augment, raht, anchor  # noqa: F401
+from . import synthetic, utils, parallel, render, augment, raht, anchor, rate_control  # noqa: F401
 
 __all__ = ["ColorModel", "SparseTensor", "CoordMap", "build", "lib", "estimate_normals", "voxelize", "downsample", "Voxelized"]

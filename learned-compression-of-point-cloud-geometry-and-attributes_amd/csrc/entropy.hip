@@ -8,11 +8,11 @@
 // (channel-major) — the flattening order of the reference's (1, C, N) tensors, hence the symbol
 // order inside each rANS stream.
 #include "common.h"
+#include "entropy_prep.h"
 
 namespace pcc {
 
 constexpr float LIKELIHOOD_BOUND = 1e-9f;
-constexpr float SCALE_BOUND = 0.11f;
 
 __global__ __launch_bounds__(256) void eb_quantize_kernel(const float* __restrict__ z, int64_t n, int c,
                                                           const float* __restrict__ med, int32_t* __restrict__ sym,
@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void eb_quantize_kernel(const float* __restric
         const int64_t row = e / c;
         const int ch = (int)(e - row * c);
         const float m = med[ch];
-        const float q = rintf(z[e] - m);
+        const float q = eb_symbol_f(z[e], m);
         if (sym) sym[(int64_t)ch * n + row] = (int32_t)q;
         if (zhat) zhat[e] = q + m;
     }
@@ -92,13 +92,10 @@ __global__ __launch_bounds__(256) void gc_encode_prep_kernel(const float* __rest
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
         const int64_t row = e / c;
         const int ch = (int)(e - row * c);
-        const float scale = fmaxf(params[row * 2 * c + ch], SCALE_BOUND);
         const float mean = params[row * 2 * c + c + ch];
-        int ix = levels - 1;
-        for (int i = 0; i < levels - 1; ++i) ix -= (scale <= tb[i]) ? 1 : 0;
         const int64_t o = (int64_t)ch * n + row;
-        idx[o] = ix;
-        if (sym) sym[o] = (int32_t)rintf(y[e] - mean);
+        idx[o] = gc_scale_index(params[row * 2 * c + ch], tb, levels);
+        if (sym) sym[o] = gc_symbol(y[e], mean);
     }
 }
 
@@ -132,14 +129,11 @@ __global__ __launch_bounds__(256) void gc_encode_prep_packed_kernel(const float*
         const int64_t j = e / c;
         const int ch = (int)(e - j * c);
         const int64_t row = perm ? perm[j] : j;
-        const float scale = fmaxf(params[row * 2 * c + ch], SCALE_BOUND);
         const float mean = params[row * 2 * c + c + ch];
-        int ix = levels - 1;
-        for (int i = 0; i < levels - 1; ++i) ix -= (scale <= tb[i]) ? 1 : 0;
         const int64_t o = (int64_t)ch * n + j;
-        idx[o] = (uint8_t)ix;
+        idx[o] = (uint8_t)gc_scale_index(params[row * 2 * c + ch], tb, levels);
         if (sym) {
-            const float sv = rintf(y[row * c + ch] - mean);
+            const float sv = gc_symbol_f(y[row * c + ch], mean);
             if (!(sv >= -32768.0f && sv <= 32767.0f)) atomicOr(overflow, 1);
             sym[o] = (int16_t)fminf(fmaxf(sv, -32768.0f), 32767.0f);
         }

@@ -499,4 +499,24 @@ int pcc_pmf_to_quantized_cdf(const float* pmf, int32_t n, int32_t precision, int
     return PCC_OK;
 }
 
+// The cost of every slot of every table in Q16 bits, what the code-length kernels (csrc/code_length.hip) gather: slot v of
+// table t costs 16 - log2(freq) bits with freq exactly as build_enc_tables reads it (the low 16 bits of cdf[v + 1] - cdf[v]);
+// slot cdf_sizes[t] - 2 is the escape symbol.  A frequency the coder refuses (0) and the unused tail of a row hold -1.
+int pcc_code_length_tables_build(const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes, int32_t n_tables, int32_t* out) {
+    const char* who = "pcc_code_length_tables_build";
+    if (!cdfs || !cdf_sizes || !out || n_tables < 1 || cdf_stride < 2) { pcc::set_error("%s: bad arguments", who); return PCC_ERR_ARG; }
+    for (int32_t t = 0; t < n_tables; ++t) {
+        if (cdf_sizes[t] < 2 || cdf_sizes[t] > cdf_stride) { pcc::set_error("%s: table %d has %d entries (2 .. %d)", who, t, cdf_sizes[t], cdf_stride); return PCC_ERR_ARG; }
+        const int32_t* cdf = cdfs + (int64_t)t * cdf_stride;
+        int32_t* row = out + (int64_t)t * cdf_stride;
+        for (int32_t v = 0; v < cdf_stride; ++v) {
+            row[v] = -1;
+            if (v > cdf_sizes[t] - 2) continue;
+            const uint32_t freq = (uint32_t)(cdf[v + 1] - cdf[v]) & 0xFFFFu;
+            if (freq) row[v] = (int32_t)std::llround(65536.0 * ((double)kPrecision - std::log2((double)freq)));
+        }
+    }
+    return PCC_OK;
+}
+
 }  // extern "C"

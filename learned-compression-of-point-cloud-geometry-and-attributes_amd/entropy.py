@@ -282,6 +282,70 @@ def check_stream_status():
                          "the stream is corrupt or was coded with other tables")
 
 
+# ---- code length without coding (DESIGN.md "Target-rate coding") ------------------------------------------------------
+class CodeLength:
+    """What a code-length launch (csrc/code_length.hip) returns: views of its one device int64 [C + 3] result, nothing read back.
+    ``q16_bits_per_channel`` [C]: the exact table cost in 1/65536 bit; ``ops``: coder operations (symbols + bypass puts);
+    ``escapes``: symbols coded through the escape slot; ``flags``: 0, or bit 1 = table index out of range, bit 2 = a slot of
+    frequency 0 was hit (the sums are then unspecified).  ``symbols`` is the host-known number of symbols N * C."""
+    __slots__ = ("raw", "q16_bits_per_channel", "ops", "escapes", "flags", "symbols")
+
+    def __init__(self, raw, c, symbols):
+        self.raw = raw
+        self.q16_bits_per_channel, self.ops, self.escapes, self.flags = raw[:c], raw[c], raw[c + 1], raw[c + 2]
+        self.symbols = int(symbols)
+
+
+# E of stream_bytes_interval, per coder operation, in 1/65536 bit, as the fraction OP_SLACK_NUM / OP_SLACK_DEN:
+#   2^16 * -log2(1 - 2^-15) = 2.885434...   (one put moves log2(x) off its ideal step by at most that: see the docstring)
+# + 0.5                                      (the rounding of one table cost to Q16)
+# = 3.385434... <= 3386 / 1000
+OP_SLACK_NUM, OP_SLACK_DEN = 3386, 1000
+_WORD_Q16 = 32 << 16
+
+
+def stream_bytes_interval(q16_bits, ops, lanes=0, symbols=None):
+    """The closed interval ``(lo, hi)`` of byte lengths that a range-coded stream can have, given its exact table cost
+    ``q16_bits`` (the sum of a CodeLength's ``q16_bits_per_channel``, in 1/65536 bit) and its ``ops`` coder operations.  Pure
+    integer arithmetic; derived from the coder (csrc/rans_host.cpp: put_sym, put_bits, rans_encode_run), not measured.
+
+    One stream.  The state x starts at 2^31.  Each put first moves the low word of x out (x >>= 32) when it would overflow
+    otherwise, which happens only while x >= 2^47 f, then maps x to floor(x / f) 2^16 + (x mod f) + start (a table put of
+    frequency f; a bypass put is the case f = 2^12 with x 16 + value).  Against the ideal x 2^16 / f that is off by a relative
+    error of at most f / x' <= 2^-15 in either direction, x' >= max(2^31, 2^15 f) being the state the put divides.  So with W
+    words moved out, L = 32 W + log2(x) grows by 16 - log2(f) per put up to +-d, d = -log2(1 - 2^-15) <= 2^-15 log2(e)
+    (1 + 2^-15).  It starts at 31 and the final x lies in [2^31, 2^63); the stream is W words and the two of the final state:
+
+        bytes = 8 + 4 W,     S - 32 - E  <  32 W  <=  S + E,     E = ops * (d + 2^-17),
+
+    S being ``q16_bits / 65536``; the 2^-17 per operation covers the rounding of a table cost to Q16 (bypass costs are exact).
+    In integers: E16 = ceil(ops * 3386 / 1000) (2^16 d + 0.5 = 3.385434... per operation), W in
+    [max(0, floor((q16_bits - E16) / 2^21)), floor((q16_bits + E16) / 2^21)].  The width is at most 4 bytes plus
+    2 E / 8 = ops * 3386 / (1000 * 2^18) bytes: 4 bytes + 1 byte per 77,418 operations.  ops = 0 gives (8, 8).
+
+    ``lanes`` > 0: the lane-parallel container (PCL1) of 8 + 4 lanes header bytes and one such stream per lane that holds a
+    symbol; an empty lane has 0 bytes.  Summed over the m non-empty lanes: total words in [floor((q16 - E16) / 2^21) - (m - 1),
+    floor((q16 + E16) / 2^21)] and 8 m bytes of final states.  m = min(lanes, symbols); when ``symbols`` is not given, the
+    interval covers every m from 1 (0 if ops is 0) to min(lanes, ops).
+    """
+    q16_bits, ops, lanes = int(q16_bits), int(ops), int(lanes)
+    if q16_bits < 0 or ops < 0 or lanes < 0:
+        raise ValueError("stream_bytes_interval: negative argument")
+    e16 = (ops * OP_SLACK_NUM + OP_SLACK_DEN - 1) // OP_SLACK_DEN
+    w_hi = (q16_bits + e16) // _WORD_Q16
+    w_lo = (q16_bits - e16) // _WORD_Q16           # = floor((S - 32 - E) / 32) + 1, the least integer above the open end
+    if lanes == 0:
+        return 8 + 4 * max(w_lo, 0), 8 + 4 * w_hi
+    head = 8 + 4 * lanes
+    if symbols is None:
+        m_lo, m_hi = min(1, ops), min(lanes, ops)
+    else:
+        m_lo = m_hi = min(lanes, int(symbols))
+    if m_hi == 0:
+        return head, head
+    return head + 8 * m_lo + 4 * max(w_lo - (m_lo - 1), 0), head + 8 * m_hi + 4 * w_hi
+
+
 class _EntropyModelBase(nn.Module):
     def __init__(self, likelihood_bound=1e-9, entropy_coder_precision=16):
         super().__init__()
@@ -299,6 +363,7 @@ class _EntropyModelBase(nn.Module):
         self._offset = torch.from_numpy(offset).to(dev)
         self._host_tables = (np.ascontiguousarray(cdf), np.ascontiguousarray(cdf_length), np.ascontiguousarray(offset))
         self.__dict__["_lane_tables"] = {}
+        self.__dict__["_cost_tables"] = {}
 
     def lane_tables(self, device):
         """The coding tables of the lane-parallel coder on ``device`` (pcc_rans_lanes_tables_build): built at the first use after
@@ -314,6 +379,34 @@ class _EntropyModelBase(nn.Module):
             check(L.pcc_rans_lanes_tables_build(ptr(cdf), cdf.shape[1], ptr(cdf_len), ptr(off), cdf_len.size, ptr(host), nbytes))
             blob = cache[device] = torch.from_numpy(host).to(device)
         return blob
+
+    def cost_tables(self, device):
+        """The Q16 cost of every slot of every coding table on ``device`` (pcc_code_length_tables_build): int32
+        [n_tables, cdf_stride], ``cost[t][v] = round(65536 * (16 - log2(freq)))`` for the slots 0 .. cdf_length[t] - 2 (the last
+        one is the escape symbol), -1 where the coder would refuse the slot (frequency 0) and in the unused tail of a row.
+        Built at the first use after update() / a checkpoint load and kept there, like lane_tables."""
+        return self._cost_tables_on(device)[0]
+
+    def _cost_tables_on(self, device):
+        """-> (cost, cdf_length, offset) on ``device``, int32: what the code-length kernels read"""
+        cache = self.__dict__.setdefault("_cost_tables", {})
+        device = torch.device(device)
+        hit = cache.get(device)
+        if hit is None:
+            cdf, cdf_len, off = self.tables()
+            cost = np.empty_like(cdf)
+            check(_lib.lib().pcc_code_length_tables_build(ptr(cdf), cdf.shape[1], ptr(cdf_len), cdf_len.size, ptr(cost)))
+            hit = cache[device] = tuple(torch.from_numpy(a).to(device) for a in (cost, cdf_len, off))
+        return hit
+
+    def code_length_planes(self, symbols, indexes):
+        """The code length of int32 planes [C, N] that exist already (any column order) -> CodeLength."""
+        c, n = symbols.shape
+        cost, cdf_len, off = self._cost_tables_on(symbols.device)
+        out = torch.empty(c + 3, dtype=torch.int64, device=symbols.device)
+        check(_lib.lib().pcc_code_length_planes(ptr(symbols.contiguous()), ptr(indexes.contiguous()), n, c, ptr(cost), cost.shape[1],
+                                                ptr(cdf_len), ptr(off), cost.shape[0], ptr(out), _lib.stream()))
+        return CodeLength(out, c, n * c)
 
     def tables(self):
         if self._host_tables is None:
@@ -333,6 +426,7 @@ class _EntropyModelBase(nn.Module):
                 setattr(self, name, state_dict[key].clone().to(getattr(self, name).device))
         self._host_tables = None
         self.__dict__["_lane_tables"] = {}
+        self.__dict__["_cost_tables"] = {}
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
 
@@ -435,6 +529,18 @@ class EntropyBottleneck(_EntropyModelBase):
         check(_lib.lib().pcc_eb_quantize(ptr(z_feats.contiguous()), n, c, ptr(self.medians()), ptr(sym), ptr(zhat),
                                          _lib.stream()))
         return sym, zhat
+
+    def code_length(self, z_feats):
+        """What compress_features would spend on z_feats [N, C], without coding it -> CodeLength (device tensors; nothing is
+        read back, no plane written)."""
+        n, c = z_feats.shape
+        cost, cdf_len, off = self._cost_tables_on(z_feats.device)
+        if cost.shape[0] != c:
+            raise ValueError(f"code_length: {c} channels, but the model holds {cost.shape[0]} tables")
+        out = torch.empty(c + 3, dtype=torch.int64, device=z_feats.device)
+        check(_lib.lib().pcc_eb_code_length(ptr(z_feats.contiguous()), n, c, ptr(self.medians()), ptr(cost), cost.shape[1], ptr(cdf_len),
+                                            ptr(off), ptr(out), _lib.stream()))
+        return CodeLength(out, c, n * c)
 
     def likelihood_features(self, zhat_feats):
         """z_hat [N, C] -> likelihood plane [C, N]."""
@@ -598,6 +704,20 @@ class GaussianConditional(_EntropyModelBase):
         check(_lib.lib().pcc_gc_encode_prep(None, ptr(params.contiguous()), n, c, ptr(table), table.numel(), None,
                                             ptr(idx), _lib.stream()))
         return idx
+
+    def code_length(self, y_feats, params):
+        """What compress_features would spend on y_feats [N, C] under params [N, 2C], without coding it -> CodeLength (device
+        tensors; nothing is read back, no plane written, no row order needed: a sum does not depend on it)."""
+        n, c = y_feats.shape
+        dev = y_feats.device
+        table = self.scale_table.to(dev).contiguous()
+        cost, cdf_len, off = self._cost_tables_on(dev)
+        if cost.shape[0] != table.numel():
+            raise ValueError(f"code_length: {table.numel()} scale levels, but the model holds {cost.shape[0]} tables")
+        out = torch.empty(c + 3, dtype=torch.int64, device=dev)
+        check(_lib.lib().pcc_gc_code_length(ptr(y_feats.contiguous()), ptr(params.contiguous()), n, c, ptr(table), table.numel(), ptr(cost),
+                                            cost.shape[1], ptr(cdf_len), ptr(off), ptr(out), _lib.stream()))
+        return CodeLength(out, c, n * c)
 
     def compress_features(self, y_feats, params, perm=None):
         sym, idx = self.encode_prep(y_feats, params)

@@ -28,6 +28,17 @@ def _c(cin, cout, k=3, s=1, bias=False):
     return MinkowskiConvolution(in_channels=cin, out_channels=cout, kernel_size=k, stride=s, bias=bias, dimension=3)
 
 
+def _estimate(self, y):
+    """``estimate(y)`` of both hyperpriors: what compress(y) would spend, without coding — h_a, the quantised z, h_s at y's
+    coordinates and the two code-length launches -> (entropy.CodeLength of y, of z).  No sort, no packed plane, no host coder,
+    no host wait: the results stay on the device."""
+    z = self.h_a(y)
+    _, z_hat_f = self.entropy_bottleneck.quantize_features(z.F, want_symbols=False)
+    z_hat = SparseTensor(z_hat_f, coordinate_map=z.map)
+    y_length = self.gaussian_conditional.code_length(y.F, self._params_at(z_hat, y.map))
+    return y_length, self.entropy_bottleneck.code_length(z.F)
+
+
 class MeanScaleHyperprior(nn.Module):
     """``MeanScaleHyperprior`` (/root/reference/model/entropy_models.py:104-250): h_a, factorized z, h_s, Gaussian y — the entropy model
     of the two-hyperprior variant of ColorModel (model/model.py:22-24: one instance codes y, a second the stride-8 q-map).  The layers
@@ -94,6 +105,8 @@ class MeanScaleHyperprior(nn.Module):
         z_strings = finish_z()
         y_strings = finish_y()
         return points, [y_strings, z_strings], shape
+
+    estimate = _estimate
 
     def decompress(self, points, strings, shape):
         """entropy_models.py:215-250 -> y_hat on the canonically sorted stride-8 coordinates; ``points`` = [coords8, coords32]
@@ -201,6 +214,8 @@ class MeanScaleHyperprior_Map(nn.Module):
         z_strings = finish_z()
         y_strings = finish_y()
         return points, [y_strings, z_strings], shape
+
+    estimate = _estimate
 
     def decompress(self, points, strings, shape, finish_z=None):
         """entropy_models.py:384-414 -> (y_hat, Q_hat); ``points`` = [coords8, coords32] or CoordMaps.  ``finish_z``: what

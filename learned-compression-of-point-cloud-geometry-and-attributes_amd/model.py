@@ -70,13 +70,9 @@ class ColorModel(nn.Module):
         return {"prediction": x_hat, "points": points, "occ_predictions": predictions, "q_map": Lambda,
                 "likelihoods": likelihoods}
 
-    # -- model/model.py:95-147 -------------------------------------------------------------------------
-    @torch.no_grad()
-    def compress(self, x, Q, path=None, batch=None):
-        """``batch`` (int [N] device tensor, optional; not in the reference's signature): item index per point
-        for the spatial-blocks-as-batch-items mode of SURVEY.md §8e — k and top-k are per item
-        (transforms.py:65-71, blocks.py:130-150), one (y, z) stream pair covers all items; ``k`` then holds
-        one count per item and stage, and ``coordinates`` carries the item index in column 0."""
+    def _analyse(self, x, Q, batch=None, path=None):
+        """The front of compress and of estimate_bits: the input map with its duplicate count armed, and g_a ->
+        (in_map, y, Q8, k)."""
         N = x.shape[0]
         dev = x.device
         if N == 0 or x.dim() != 2 or x.shape[1] < 6:
@@ -97,6 +93,17 @@ class ColorModel(nn.Module):
         if Q.map._nbatch is None:
             Q.map._nbatch = nbatch
         y, Q8, k = self.g_a(inp, Q)
+        return in_map, y, Q8, k
+
+    # -- model/model.py:95-147 -------------------------------------------------------------------------
+    @torch.no_grad()
+    def compress(self, x, Q, path=None, batch=None):
+        """``batch`` (int [N] device tensor, optional; not in the reference's signature): item index per point
+        for the spatial-blocks-as-batch-items mode of SURVEY.md §8e — k and top-k are per item
+        (transforms.py:65-71, blocks.py:130-150), one (y, z) stream pair covers all items; ``k`` then holds
+        one count per item and stage, and ``coordinates`` carries the item index in column 0."""
+        in_map, y, Q8, k = self._analyse(x, Q, batch, path)
+        N = x.shape[0]
         if self.entropy_model_map is None:
             points, strings, shape = self.entropy_model.compress(y)
         else:
@@ -117,6 +124,39 @@ class ColorModel(nn.Module):
             self.save_bitstream(path=path, points=coordinates, strings=strings, shape=shape, k=k)
             return None
         return strings, shape, k, coordinates
+
+    @torch.no_grad()
+    def estimate_bits(self, x, Q, batch=None):
+        """What ``compress(x, Q, batch=batch)`` would spend on its y and z strings, without coding them: the same front (input
+        map, duplicate check, g_a), then ``entropy_model.estimate`` instead of the coder.  -> ``{"y": (lo, hi), "z": (lo, hi),
+        "bytes": (lo, hi), "escapes": int, "n_points": N}``: closed byte intervals (entropy.stream_bytes_interval) that
+        ``len(strings[0][0])``, ``len(strings[1][0])`` and their sum lie in, for the stream format in force
+        (entropy.STREAM_LANES); the two-hyperprior variant sums both models' strings.  One small read from the device at the end."""
+        in_map, y, Q8, _ = self._analyse(x, Q, batch)
+        lengths = list(self.entropy_model.estimate(y))
+        if self.entropy_model_map is not None:
+            lengths += list(self.entropy_model_map.estimate(Q8))
+        words = [cl.raw for cl in lengths]
+        if in_map._dup_word is not None and in_map._table is not None:
+            words.append(in_map._dup_word.to(torch.int64))
+        host = torch.cat(words).cpu().tolist()
+        if len(words) > len(lengths) and host[-1]:
+            raise ValueError(f"estimate_bits: {host[-1]} of the {x.shape[0]} points repeat the voxel coordinates of an earlier point "
+                             "(see compress)")
+        out = {"y": (0, 0), "z": (0, 0), "escapes": 0, "n_points": int(x.shape[0])}
+        at = 0
+        for i, cl in enumerate(lengths):
+            c = cl.q16_bits_per_channel.numel()
+            q16, ops, escapes, flags = sum(host[at:at + c]), host[at + c], host[at + c + 1], host[at + c + 2]
+            at += c + 3
+            if flags:
+                raise ValueError(f"estimate_bits: the code-length kernel reports {flags:#x} ({_entropy._lane_flag_text(flags)})")
+            key = "yz"[i % 2]                                      # the y stream alone takes the lane format (entropy.STREAM_LANES)
+            lo, hi = _entropy.stream_bytes_interval(q16, ops, _entropy.STREAM_LANES if key == "y" else 0, symbols=cl.symbols)
+            out[key] = (out[key][0] + lo, out[key][1] + hi)
+            out["escapes"] += escapes
+        out["bytes"] = (out["y"][0] + out["z"][0], out["y"][1] + out["z"][1])
+        return out
 
     # -- model/model.py:152-208 ------------------------------------------------------------------------
     @torch.no_grad()

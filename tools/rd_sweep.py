@@ -6,12 +6,15 @@ Seeded random weights in their q-RESPONSIVE variant (synthetic.FILM_GAIN_Q_RESPO
 follows the quality map; PCC_SWEEP_FILM_GAIN overrides): the rate axis is a real sweep, the distortion axis is that of random
 weights — not codec quality.
 
-usage: rd_sweep.py [--d2 R] [--downsample F] [--anchor] [out.json] [weights.pt]
+usage: rd_sweep.py [--d2 R] [--downsample F] [--anchor] [--target-bpp B [B ...]] [out.json] [weights.pt]
   --d2 R: add the point-to-plane PSNR, normals over R voxels
   --downsample F: code every frame on a grid F times coarser (pcc_amd.voxelize: exact mean colours; the reference's "QA" factors
                   are 1, 2, 4, 8), metrics against the down-sampled source
   --anchor: also code every frame with the octree + RAHT anchor codec (pcc_amd.anchor) at qstep = {2, 4, 8, 16, 32, 64} / 255 and
-            report the model's BD-rate and BD-PSNR (Y) against the anchor's curve of the same frame"""
+            report the model's BD-rate and BD-PSNR (Y) against the anchor's curve of the same frame
+  --target-bpp B [B ...]: add rows coded to a target instead of a q pair (pcc_amd.rate_control.compress_to_target: the y + z payload
+            in bits per input point stays at or below B); each row is the frame evaluated at the (q_g, q_a) the search chose, with
+            the target, the probe count and whether it was reached ("target_rows" of the output; the q-grid rows are unchanged)"""
 import json, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -35,6 +38,18 @@ if "--downsample" in sys.argv:
 with_anchor = "--anchor" in sys.argv
 if with_anchor:
     sys.argv.remove("--anchor")
+target_bpps = []
+if "--target-bpp" in sys.argv:
+    at = end = sys.argv.index("--target-bpp")
+    while end + 1 < len(sys.argv):
+        try:
+            target_bpps.append(float(sys.argv[end + 1]))
+        except ValueError:
+            break
+        end += 1
+    if not target_bpps:
+        sys.exit("--target-bpp needs at least one number")
+    del sys.argv[at:end + 1]
 ANCHOR_QSTEPS = [q / 255 for q in (2, 4, 8, 16, 32, 64)]
 FRAMES = {"redandblack~": 247.0, "loot~": 255.0, "longdress~": 261.5, "soldier~": 294.5}   # shell radii -> ~0.76 / 0.81 / 0.86 / 1.09 M
 QS = [(0.05, 0.1), (0.1, 0.2), (0.2, 0.4), (0.4, 0.8)]
@@ -43,7 +58,7 @@ model = syn.make_model(seed=0, device=dev, film_gain=film_gain)
 if len(sys.argv) > 2:
     model.load_state_dict(torch.load(sys.argv[2], map_location=dev))
 model.update()
-rows, anchor_rows = [], []
+rows, anchor_rows, target_rows = [], [], []
 with tempfile.TemporaryDirectory() as td:
     for name, radius in FRAMES.items():
         pts = syn.sphere_shell(grid=1024, radius=radius, half_width=0.5, noise=0.02)
@@ -56,6 +71,21 @@ with tempfile.TemporaryDirectory() as td:
             print(f"{name:13s} N={row['n_source']:8d} q=({q_g},{q_a}) bpp {row['bpp']:.3f} D1 {row['sym_p2p_psnr']:.2f} Y {row['sym_y_psnr']:.2f} "
                   + (f"D2 {row['sym_d2_psnr']:.2f} " if d2_radius is not None else "") +
                   f"t_enc {row['t_compress']*1e3:.0f} ms t_dec {row['t_decompress']*1e3:.0f} ms (row {time.time()-t0:.1f} s)", flush=True)
+        for bpp in target_bpps:
+            from pcc_amd.harness import downsample_frame
+            from pcc_amd.rate_control import compress_to_target
+            t0 = time.time()
+            coded = data if downsample is None else downsample_frame(data, downsample, dev)[0]
+            src = torch.cat([coded["src"]["points"], coded["src"]["colors"]], dim=2)[0].to(dev, dtype=torch.float)
+            found = compress_to_target(model, src, target_bpp=bpp)
+            q_g, q_a = found["q"]
+            row = evaluate_frame("sweep", model, data, q_a, q_g, dev, td, d2_radius=d2_radius, downsample=downsample)
+            row.update(frame=name, target_bpp=bpp, target_reached=found["reached"], t=found["t"], probes=len(found["log"]),
+                       payload_bpp=found["bytes"] * 8 / src.shape[0], estimate_bpp=found["estimate"] * 8 / src.shape[0])
+            target_rows.append(row)
+            print(f"{name:13s} N={row['n_source']:8d} target {bpp} bpp -> q=({q_g:.4f},{q_a:.4f}) payload {row['payload_bpp']:.3f} bpp "
+                  f"({'reached' if found['reached'] else 'NOT reached'}, {row['probes']} probes) file {row['bpp']:.3f} bpp Y {row['sym_y_psnr']:.2f} "
+                  f"(row {time.time()-t0:.1f} s)", flush=True)
         for qstep in (ANCHOR_QSTEPS if with_anchor else ()):
             t0 = time.time()
             row = evaluate_anchor(data, qstep, dev, downsample=downsample)
@@ -98,6 +128,7 @@ out = {"rows": rows, "bjontegaard": bd,
                f" (FiLM-head gain {film_gain}); synthetic shells sized like the 8iVFB frames",
        **({"anchor_rows": anchor_rows, "anchor": "octree + RAHT (pcc_amd.anchor): lossless PCO1 geometry, BT.709 YUV attributes, "
                                                   "qstep = {2, 4, 8, 16, 32, 64} / 255"} if with_anchor else {}),
+       **({"target_rows": target_rows} if target_bpps else {}),
        "rate_axis_monotone_in_q": {nm: [r["bpp"] for r in rows if r["frame"] == nm] == sorted(r["bpp"] for r in rows if r["frame"] == nm)
                                    for nm in names}}
 path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "rd_sweep.json")
