@@ -70,7 +70,9 @@ int64_t pcc_hash_capacity(int64_t n);
 int pcc_hash_build(const int32_t* coords, int64_t n, uint64_t* keys, int32_t* vals, int64_t cap,
                    int32_t tensor_stride, int32_t* dup_count, void* stream);
 
-/* out_idx[i] = row of query i or -1.  (features_at_coordinates on on-grid integer queries:
+/* out_idx[i] = row of query i or -1.  A query with a coordinate beyond PCC_COORD_LIMIT or a batch index outside
+ * 0 .. PCC_BATCH_LIMIT is in no set: it gets -1, never the row of the voxel its masked key would alias.
+ * (features_at_coordinates on on-grid integer queries:
  * model/transforms.py:96,124,262; model/blocks.py:37,50; model/entropy_models.py:326,364,401;
  * torch.isin of model/blocks.py:125.) */
 int pcc_hash_lookup(const uint64_t* keys, const int32_t* vals, int64_t cap, int32_t tensor_stride,

@@ -314,7 +314,8 @@ __global__ __launch_bounds__(256) void lookup_kernel(const uint64_t* __restrict_
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nq) return;
     const int4 c = reinterpret_cast<const int4*>(query)[i];
-    out_idx[i] = table_find(keys, vals, mask, shift, pack_key(c.x, c.y, c.z, c.w));
+    // a query outside the key range is in no set: pack_key masks every field, so its key would be another voxel's
+    out_idx[i] = coord_in_range(c.x, c.y, c.z, c.w) ? table_find(keys, vals, mask, shift, pack_key(c.x, c.y, c.z, c.w)) : -1;
 }
 
 // One 256-thread block per group of 64 output rows: 64*K probes, coalesced nbr stores, row masks reduced in LDS.

@@ -11,6 +11,7 @@ import torch
 from oracle import coords as oc
 from oracle import nn as on
 from oracle import entropy as oe
+from _coord_cases import order_key        # the one restatement of the execution-order key (csrc/select.hip)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -149,18 +150,6 @@ def _nbr_as_coords(nbr, in_coords):
     hit = nbr >= 0
     out[hit] = in_coords[nbr[hit]]
     return out
-
-
-def order_key(masks):
-    """the execution-order key of csrc/select.hip: the 27-bit neighbour mask read with the rarest offset as the most
-    significant bit (ties: lower offset first), descending"""
-    masks = np.asarray(masks, dtype=np.int64) & 0x7FFFFFF
-    cnt = np.array([int(((masks >> b) & 1).sum()) for b in range(27)])
-    pos = [26 - sum(1 for o in range(27) if cnt[o] < cnt[b] or (cnt[o] == cnt[b] and o < b)) for b in range(27)]
-    key = np.zeros(masks.shape[0], dtype=np.int64)
-    for b in range(27):
-        key |= ((masks >> b) & 1) << pos[b]
-    return 0x7FFFFFF - key
 
 
 @pytest.mark.parametrize("case", ["same", "down", "up3", "up2", "cross"])
