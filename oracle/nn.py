@@ -90,7 +90,7 @@ def _apply_conv(F_in, W, bias, nbr, n_out):
     assert W.shape[0] == K, (W.shape, K)
     if ORDER == "kernel":
         return _apply_conv_kernel_order(F_in, W, bias, nbr, n_out)
-    out = torch.zeros((n_out, W.shape[2]), dtype=torch.float32)
+    out = torch.zeros((n_out, W.shape[2]), dtype=torch.result_type(F_in, W))       # (float64 operands: the exact-gradient tests)
     for k in range(K):
         col = nbr[:, k]
         rows = np.nonzero(col >= 0)[0]

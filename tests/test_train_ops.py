@@ -322,5 +322,14 @@ def test_transposed_ordered_map_equals_the_direct_calls(pcc, kind):
     for name, a, b in zip(("nbr_t", "order", "gmask"), got, (nbr_t, order, gmask)):
         assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), name
     assert torch.equal(torch.sort(got[1].long()).values, torch.arange(n_in, device=DEV))       # a permutation of the input rows
+    # ... and nbr_t is the numpy transposition of the ORACLE's map (product output rows matched to the oracle's by coordinate)
+    from _conv_grad_cases import transpose_reference
+    c_in = m.coords.cpu().numpy()
+    c_out = oc.stride_map(c_in, 2) if kind == "down" else oc.children(c_in, 2, 3)
+    want_t, _ = transpose_reference(oc.kernel_map(c_in, c_out, 3, 2 if kind == "down" else 1, transposed=tr), n_in)
+    idx = oc.lookup(c_out, out_map.coords.cpu().numpy())
+    assert n_out == c_out.shape[0] and np.array_equal(np.sort(idx), np.arange(n_out))
+    t = got[0].cpu().numpy()
+    assert np.array_equal(np.where(t >= 0, idx[np.maximum(t, 0)], -1), want_t)
     again = m.transposed_ordered_map(out_map, 3, tr)
     assert all(a is b for a, b in zip(again, got))
