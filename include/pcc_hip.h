@@ -492,6 +492,47 @@ int pcc_estimate_normals(const int32_t* coords, int64_t n, const uint64_t* keys,
                          double* normals, int32_t* count, int64_t* moments, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Perceptual metric "pcqm_voxel": PCQM's structure (Meynet, Nehme, Digne, Lavoue, QoMEX 2020) on a voxel
+ * grid.  A stand-in for the external PCQM binary of the reference's sweep (utils.py:290-344); it does NOT
+ * reproduce that binary's numbers (plain CIELAB instead of LAB2000HL, surface variation instead of a quadric's
+ * mean curvature, nearest voxel instead of a projection onto a quadric).
+ *
+ * pcc_surface_variation: kappa [n] (f64) = l0 / (l0 + l1 + l2), l0 <= l1 <= l2 the eigenvalues of the moment
+ * matrix M of pcc_estimate_normals over the radius-`radius` ball (1..8), by the same fixed-order Jacobi
+ * (bitwise reproducible; an l0 below zero counts as 0); 0 where pcc_estimate_normals gives no normal.
+ * coords / keys / vals / cap / tensor_stride: one cloud and its own table.
+ *
+ * pcc_pcqm_features: one logical work item per row p of the reference cloud R (coords_r [n_r,4] and its
+ * table); D (coords_d [n_d,4] and its table) is the distorted cloud, nn [n_r] the row of p's nearest D voxel
+ * p^.  attrs_r [n_r,5] / attrs_d [n_d,5] (f64): (L, c, a, b, kappa) per row.  w: h^2 + 1 device doubles, the
+ * weight of a neighbour at squared distance d2 is w[d2] (h: 1..8).  constants: 4 HOST doubles (k_L, k_kappa,
+ * c_chroma, c_hue).  N_R(p) = rows q of R with |q - p|^2 <= h^2, N_D(p^) likewise in D, centres included,
+ * each ball walked once in ascending (dx, dy, dz).  Outputs (device f64, each may be NULL, not all three):
+ *   stats [n_r,18]: sum of w over N_R, over N_D; the weighted means of L, c, a, b, kappa over N_R, then over
+ *     N_D; then v_L, v^_L, s_L, v_kappa, v^_kappa, s_kappa: the weighted variances over N_R and N_D (clamped
+ *     at 0) and the cross term s_x = sum_{q in N_R} w (x_R(q) - mean_R)(x_D(nn[q]) - mean_D) / sum w.
+ *   features [n_r,8]: f1 = |mL - m^L| / (max + k_L), f2 = the same on sqrt(v_L), sqrt(v^_L),
+ *     f3 = |S - s_L| / (S + k_L) with S = sqrt(v_L v^_L), f4 = 1 - 1 / (c_chroma (mc - m^c)^2 + 1),
+ *     f5 = 1 - 1 / (c_hue dH + 1) with dH = max(0, (ma - m^a)^2 + (mb - m^b)^2 - (mc - m^c)^2), f6..f8 = f1..f3
+ *     on kappa with k_kappa.  Identical clouds give exactly 0 everywhere.
+ *   sums [8]: the sums of the features over all rows; needs scratch of pcc_pcqm_scratch_bytes(n_r) bytes (0
+ *     for an n the call refuses): workgroups store partial sums in workgroup order, a second launch adds them
+ *     in ascending order.  No float atomics: bitwise reproducible.
+ * A row index out of range (nn, or a table that belongs to another cloud) is never followed: the rows it
+ * touches come out as NaN.  Refused before any launch (PCC_ERR_ARG, the message names the argument): h or
+ * radius outside 1..8, a capacity that is no power of two, null required pointers, no output at all, a short
+ * scratch, n_d == 0 with n_r > 0.  n_r == 0 is valid and zeroes sums.
+ * ------------------------------------------------------------------------------------- */
+int pcc_surface_variation(const int32_t* coords, int64_t n, const uint64_t* keys, const int32_t* vals, int64_t cap,
+                          int32_t tensor_stride, int32_t radius, double* kappa, void* stream);
+int64_t pcc_pcqm_scratch_bytes(int64_t n);
+int pcc_pcqm_features(const int32_t* coords_r, int64_t n_r, const uint64_t* keys_r, const int32_t* vals_r, int64_t cap_r,
+                      const int32_t* coords_d, int64_t n_d, const uint64_t* keys_d, const int32_t* vals_d, int64_t cap_d,
+                      int32_t tensor_stride, const int32_t* nn, const double* attrs_r, const double* attrs_d,
+                      const double* w, int32_t h, const double* constants, double* stats, double* features, double* sums,
+                      void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * View rendering and view metrics of the view-dependent / region-of-interest evaluation
  * (evaluate_view_dep.py:102-305).
  *

@@ -32,6 +32,9 @@ NO_SCRATCH = {
                  "voxelize_accumulate_kernel"),
     # RAHT (csrc/raht.hip): a step is two gathered float64 rows in, two out; a spill would sit between the gather and the store
     "raht": ("raht_plan_kernel", "raht_step_kernel", "raht_fold_kernel"),
+    # the perceptual metric (csrc/pcqm.hip): 20 running sums per point live through up to 4,218 probes and gathers; a spilled
+    # one would put a scratch round trip behind every neighbour.  The kappa kernel shares the normals' Jacobi over named scalars
+    "pcqm": ("surface_variation_kernel", "pcqm_features_kernel"),
 }
 
 

@@ -10,53 +10,11 @@
 // iteration in float64 with a fixed pair order (0,1), (0,2), (1,2) and a fixed number of sweeps: the same input gives
 // the same bits on every run.
 //
-// Latency bound like nn_search_kernel: one thread per point, 7 / 33 / 123 / 2,109 probes at R = 1 / 2 / 3 / 8.  The 3 x 3
-// matrix and its eigenvectors are named scalars — an indexed array would live in scratch memory.
-#include "common.h"
+// Latency bound like nn_search_kernel: one thread per point, 7 / 33 / 123 / 2,109 probes at R = 1 / 2 / 3 / 8.  The ball's
+// moment loop and the Jacobi iteration live in ball_moments.h, which pcqm.hip shares.
+#include "ball_moments.h"
 
 namespace pcc {
-
-constexpr int NORMAL_SWEEPS = 12;
-constexpr int NORMAL_MAX_RADIUS = 8;
-
-// One Jacobi rotation in the (p, q) plane of a symmetric 3 x 3 matrix; r is the third index.  app, aqq, apq: the pair's
-// entries; apr, aqr: their couplings to r; (v0p, v0q), (v1p, v1q), (v2p, v2q): columns p and q of the eigenvector matrix.
-__host__ __device__ __forceinline__ void jacobi_rotate(double& app, double& aqq, double& apq, double& apr, double& aqr, double& v0p,
-                                                       double& v0q, double& v1p, double& v1q, double& v2p, double& v2q) {
-    if (apq == 0.0) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));      // the smaller root: |angle| <= pi/4
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    app -= t * apq;
-    aqq += t * apq;
-    apq = 0.0;
-    const double pr = apr, qr = aqr;
-    apr = c * pr - s * qr;
-    aqr = s * pr + c * qr;
-    const double a0 = v0p, b0 = v0q, a1 = v1p, b1 = v1q, a2 = v2p, b2 = v2q;
-    v0p = c * a0 - s * b0; v0q = s * a0 + c * b0;
-    v1p = c * a1 - s * b1; v1q = s * a1 + c * b1;
-    v2p = c * a2 - s * b2; v2q = s * a2 + c * b2;
-}
-
-// Unit eigenvector of the smallest eigenvalue of the symmetric matrix (xx xy xz; xy yy yz; xz yz zz).  Equal smallest
-// diagonal entries resolve to the lowest column.
-__host__ __device__ __forceinline__ void smallest_eigenvector(double a00, double a01, double a02, double a11, double a12, double a22,
-                                                              double& nx, double& ny, double& nz) {
-    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
-#pragma unroll 1
-    for (int sweep = 0; sweep < NORMAL_SWEEPS; ++sweep) {
-        jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);      // (0, 1), r = 2
-        jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);      // (0, 2), r = 1
-        jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);      // (1, 2), r = 0
-    }
-    double lo = a00;
-    nx = v00; ny = v10; nz = v20;
-    if (a11 < lo) { lo = a11; nx = v01; ny = v11; nz = v21; }
-    if (a22 < lo) { nx = v02; ny = v12; nz = v22; }
-    const double inv = 1.0 / sqrt(nx * nx + ny * ny + nz * nz);
-    nx *= inv; ny *= inv; nz *= inv;
-}
 
 __global__ __launch_bounds__(256) void estimate_normals_kernel(const int32_t* __restrict__ coords, int64_t n,
                                                                const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals,
@@ -66,35 +24,15 @@ __global__ __launch_bounds__(256) void estimate_normals_kernel(const int32_t* __
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int b = coords[4 * i], x = coords[4 * i + 1], y = coords[4 * i + 2], z = coords[4 * i + 3];
-    const int r2 = radius * radius;
-    int cnt = 0, sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
-    for (int dx = -radius; dx <= radius; ++dx) {
-        for (int dy = -radius; dy <= radius; ++dy) {
-            const int rest = r2 - dx * dx - dy * dy;
-            if (rest < 0) continue;
-            for (int dz = -radius; dz <= radius; ++dz) {
-                if (dz * dz > rest) continue;
-                // a coordinate below zero (or past the cloud) packs to a key no row holds: the probe misses
-                if (table_find(keys, vals, mask, shift, pack_key(b, x + dx, y + dy, z + dz)) < 0) continue;
-                ++cnt;
-                sx += dx; sy += dy; sz += dz;
-                sxx += dx * dx; sxy += dx * dy; sxz += dx * dz;
-                syy += dy * dy; syz += dy * dz; szz += dz * dz;
-            }
-        }
-    }
-    const int64_t c = cnt;
-    const int64_t mxx = c * sxx - (int64_t)sx * sx, mxy = c * sxy - (int64_t)sx * sy, mxz = c * sxz - (int64_t)sx * sz;
-    const int64_t myy = c * syy - (int64_t)sy * sy, myz = c * syz - (int64_t)sy * sz, mzz = c * szz - (int64_t)sz * sz;
-    if (count) count[i] = cnt;
+    const BallMoments m = ball_moments(keys, vals, mask, shift, b, x, y, z, radius);
+    if (count) count[i] = m.cnt;
     if (moments) {
-        int64_t* m = moments + 6 * i;
-        m[0] = mxx; m[1] = mxy; m[2] = mxz; m[3] = myy; m[4] = myz; m[5] = mzz;
+        int64_t* o = moments + 6 * i;
+        o[0] = m.xx; o[1] = m.xy; o[2] = m.xz; o[3] = m.yy; o[4] = m.yz; o[5] = m.zz;
     }
-    const int64_t minors = (mxx * myy - mxy * mxy) + (mxx * mzz - mxz * mxz) + (myy * mzz - myz * myz);
     double nx = 0.0, ny = 0.0, nz = 0.0;
-    if (cnt >= 3 && minors > 0) {
-        smallest_eigenvector((double)mxx, (double)mxy, (double)mxz, (double)myy, (double)myz, (double)mzz, nx, ny, nz);
+    if (ball_spans_a_plane(m)) {
+        smallest_eigenvector((double)m.xx, (double)m.xy, (double)m.xz, (double)m.yy, (double)m.yz, (double)m.zz, nx, ny, nz);
         double dot = 0.0;
         if (orient_mode == 1) dot = nx * ox + ny * oy + nz * oz;
         if (orient_mode == 2) dot = nx * (ox - (double)x) + ny * (oy - (double)y) + nz * (oz - (double)z);

@@ -81,9 +81,11 @@ def downsample_frame(data, factor, device, q_a=None, q_g=None):
     return small, follow(q_a), follow(q_g)
 
 
-def evaluate_frame(experiment, model, data, q_a, q_g, device, base_path, resolution=1023, d2_radius=None, downsample=None):
+def evaluate_frame(experiment, model, data, q_a, q_g, device, base_path, resolution=1023, d2_radius=None, downsample=None, pcqm=False):
     """one row of the sweep table (evaluate.py:100-160): rate, times, D1 and colour PSNRs; with ``d2_radius`` (the radius of the
-    normal estimation, in voxels) also ``sym_d2_psnr``, the point-to-plane figure of utils.py:263-288.
+    normal estimation, in voxels) also ``sym_d2_psnr``, the point-to-plane figure of utils.py:263-288; with ``pcqm`` also
+    ``pcqm_voxel`` and ``pcqm_f1`` .. ``pcqm_f8`` (pcqm.py: a voxel-grid stand-in for the PCQM column of evaluate.py:126, NOT
+    comparable with the PCQM binary's numbers).
 
     ``downsample`` (a factor, e.g. 2, 4, 8: the reference's "QA" sequences, data/utils/RawLoader.py:48-57): the frame is first
     voxelised on a grid that many times coarser (downsample_frame); source and quality map are built on the down-sampled
@@ -105,16 +107,25 @@ def evaluate_frame(experiment, model, data, q_a, q_g, device, base_path, resolut
             "sym_v_psnr": res["sym_v_psnr"]}
     if d2_radius is not None:
         row["sym_d2_psnr"] = metric.compute_d2(radius=d2_radius)["sym_d2_psnr"]
+    if pcqm:
+        row.update(_pcqm_columns(metric))
     if downsample is not None:
         row["downsample"], row["n_input"] = float(downsample), n_input
     return row
 
 
-def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, colorspace="yuv"):
+def _pcqm_columns(metric):
+    """``pcqm_voxel`` and ``pcqm_f1`` .. ``pcqm_f8`` of a PointCloudMetric: the voxel-grid stand-in (pcqm.py), not PCQM's number"""
+    res = metric.compute_pcqm()
+    return {k: v for k, v in res.items() if k.startswith("pcqm_")}
+
+
+def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, colorspace="yuv", pcqm=False):
     """one row of the sweep table for the octree + RAHT anchor codec (anchor.py) at quantisation step ``qstep``: the keys of
     ``evaluate_frame``'s row without the quality-map pair, plus ``qstep`` and ``codec``.  ``bpp`` counts the whole PCA1 stream;
     the geometry is lossless, so ``sym_p2p_psnr`` is inf and ``n_decoded`` equals ``n_source``.  ``downsample`` and
-    ``resolution`` mean what they mean in ``evaluate_frame``: the anchor's lossy-geometry rate points are coarser grids."""
+    ``resolution`` mean what they mean in ``evaluate_frame``: the anchor's lossy-geometry rate points are coarser grids; so does
+    ``pcqm``."""
     from . import anchor
     n_input = None
     if downsample is not None:
@@ -145,6 +156,8 @@ def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, color
            "n_source": int(src.shape[0]), "n_decoded": int(rec.shape[0]),
            "sym_p2p_psnr": res["sym_psnr_mse"], "sym_y_psnr": res["sym_y_psnr"], "sym_u_psnr": res["sym_u_psnr"],
            "sym_v_psnr": res["sym_v_psnr"]}
+    if pcqm:
+        row.update(_pcqm_columns(metric))
     if downsample is not None:
         row["downsample"], row["n_input"] = float(downsample), n_input
     return row

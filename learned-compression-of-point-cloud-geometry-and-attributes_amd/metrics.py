@@ -181,6 +181,22 @@ class PointCloudMetric:
         result["sym_d2_psnr"] = min(result["AB_d2_psnr"], result["BA_d2_psnr"])
         return result
 
+    def compute_pcqm(self, radius=None, neighbourhood=None, **kw):
+        """``pcqm.pcqm_voxel(source, reconstruction, ...)`` — the voxel-grid stand-in for PCQM, NOT the PCQM binary's number — on
+        the maps and the source -> reconstruction association the constructor holds: no second hash build, no second search.
+        The keyword parameters and the result are ``pcqm_voxel``'s (without ``device``); needs ``drop_duplicates=True`` clouds,
+        the constructor's default."""
+        from . import pcqm
+        defaults = {"weights": pcqm.DEFAULT_WEIGHTS, "k_L": pcqm.DEFAULT_K_L, "k_kappa": pcqm.DEFAULT_K_KAPPA,
+                    "c_chroma": pcqm.DEFAULT_C_CHROMA, "c_hue": pcqm.DEFAULT_C_HUE, "return_features": False}
+        unknown = set(kw) - set(defaults)
+        if unknown:
+            raise TypeError("compute_pcqm: unknown parameters %s" % sorted(unknown))
+        defaults.update(kw)
+        return pcqm._score(self.source_points, self.source_colors, self.source_map, self.recons_points, self.recons_colors,
+                           self.recons_map, self.source_2_recons[0], radius, neighbourhood, defaults["weights"], defaults["k_L"],
+                           defaults["k_kappa"], defaults["c_chroma"], defaults["c_hue"], defaults["return_features"])
+
     def compute_metrics(self, mirror=False, drop_duplicates=False):
         if not mirror:
             a_colors, b_colors, assoc, prefix = self.source_colors, self.recons_colors, self.source_2_recons, "AB_"

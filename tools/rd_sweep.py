@@ -6,8 +6,11 @@ Seeded random weights in their q-RESPONSIVE variant (synthetic.FILM_GAIN_Q_RESPO
 follows the quality map; PCC_SWEEP_FILM_GAIN overrides): the rate axis is a real sweep, the distortion axis is that of random
 weights — not codec quality.
 
-usage: rd_sweep.py [--d2 R] [--downsample F] [--anchor] [--target-bpp B [B ...]] [out.json] [weights.pt]
+usage: rd_sweep.py [--d2 R] [--pcqm] [--downsample F] [--anchor] [--target-bpp B [B ...]] [out.json] [weights.pt]
   --d2 R: add the point-to-plane PSNR, normals over R voxels
+  --pcqm: add ``pcqm_voxel`` (pcc_amd.pcqm: PCQM's structure on the voxel grid, a stand-in that is NOT comparable with the numbers
+          of the PCQM binary behind the reference's ``pcqm`` column) and its pooled features to every row; with --anchor also the
+          BD-rate over the quality axis 1 - pcqm_voxel against the anchor
   --downsample F: code every frame on a grid F times coarser (pcc_amd.voxelize: exact mean colours; the reference's "QA" factors
                   are 1, 2, 4, 8), metrics against the down-sampled source
   --anchor: also code every frame with the octree + RAHT anchor codec (pcc_amd.anchor) at qstep = {2, 4, 8, 16, 32, 64} / 255 and
@@ -30,6 +33,9 @@ if "--d2" in sys.argv:
     at = sys.argv.index("--d2")
     d2_radius = int(sys.argv[at + 1])
     del sys.argv[at:at + 2]
+with_pcqm = "--pcqm" in sys.argv
+if with_pcqm:
+    sys.argv.remove("--pcqm")
 downsample = None
 if "--downsample" in sys.argv:
     at = sys.argv.index("--downsample")
@@ -65,11 +71,11 @@ with tempfile.TemporaryDirectory() as td:
         data = {"src": {"points": torch.from_numpy(pts[None, :, :3]), "colors": torch.from_numpy(pts[None, :, 3:])}}
         for q_g, q_a in QS:
             t0 = time.time()
-            row = evaluate_frame("sweep", model, data, q_a, q_g, dev, td, d2_radius=d2_radius, downsample=downsample)
+            row = evaluate_frame("sweep", model, data, q_a, q_g, dev, td, d2_radius=d2_radius, downsample=downsample, pcqm=with_pcqm)
             row["frame"] = name
             rows.append(row)
             print(f"{name:13s} N={row['n_source']:8d} q=({q_g},{q_a}) bpp {row['bpp']:.3f} D1 {row['sym_p2p_psnr']:.2f} Y {row['sym_y_psnr']:.2f} "
-                  + (f"D2 {row['sym_d2_psnr']:.2f} " if d2_radius is not None else "") +
+                  + (f"D2 {row['sym_d2_psnr']:.2f} " if d2_radius is not None else "") + (f"pcqm_voxel {row['pcqm_voxel']:.5f} " if with_pcqm else "") +
                   f"t_enc {row['t_compress']*1e3:.0f} ms t_dec {row['t_decompress']*1e3:.0f} ms (row {time.time()-t0:.1f} s)", flush=True)
         for bpp in target_bpps:
             from pcc_amd.harness import downsample_frame
@@ -79,7 +85,7 @@ with tempfile.TemporaryDirectory() as td:
             src = torch.cat([coded["src"]["points"], coded["src"]["colors"]], dim=2)[0].to(dev, dtype=torch.float)
             found = compress_to_target(model, src, target_bpp=bpp)
             q_g, q_a = found["q"]
-            row = evaluate_frame("sweep", model, data, q_a, q_g, dev, td, d2_radius=d2_radius, downsample=downsample)
+            row = evaluate_frame("sweep", model, data, q_a, q_g, dev, td, d2_radius=d2_radius, downsample=downsample, pcqm=with_pcqm)
             row.update(frame=name, target_bpp=bpp, target_reached=found["reached"], t=found["t"], probes=len(found["log"]),
                        payload_bpp=found["bytes"] * 8 / src.shape[0], estimate_bpp=found["estimate"] * 8 / src.shape[0])
             target_rows.append(row)
@@ -88,7 +94,7 @@ with tempfile.TemporaryDirectory() as td:
                   f"(row {time.time()-t0:.1f} s)", flush=True)
         for qstep in (ANCHOR_QSTEPS if with_anchor else ()):
             t0 = time.time()
-            row = evaluate_anchor(data, qstep, dev, downsample=downsample)
+            row = evaluate_anchor(data, qstep, dev, downsample=downsample, pcqm=with_pcqm)
             row["frame"] = name
             anchor_rows.append(row)
             print(f"{name:13s} N={row['n_source']:8d} anchor qstep {qstep * 255:.0f}/255 bpp {row['bpp']:.3f} Y {row['sym_y_psnr']:.2f} "
@@ -123,12 +129,25 @@ for nm in (names if with_anchor else ()):
             entry["error_vs_anchor"] = entry.get("error_vs_anchor", "") + " the rate ranges do not overlap: no BD-PSNR"
     except Exception as e:      # curves that do not overlap, or degenerate fits
         entry["error_vs_anchor"] = repr(e)
+    if with_pcqm:               # the same delta over the quality axis 1 - pcqm_voxel (higher = better, like a PSNR)
+        try:
+            m1 = Bjontegaard_Model([r["bpp"] for r in anc], [1.0 - r["pcqm_voxel"] for r in anc])
+            m2 = Bjontegaard_Model([r["bpp"] for r in cur], [1.0 - r["pcqm_voxel"] for r in cur])
+            if max(m1.psnr_values.min(), m2.psnr_values.min()) < min(m1.psnr_values.max(), m2.psnr_values.max()):
+                entry["bd_rate_pcqm_voxel_vs_anchor"] = float(Bjontegaard_Delta().compute_BD_Rate(m1, m2))
+            else:
+                entry["bd_rate_pcqm_voxel_vs_anchor"] = None
+                entry["error_pcqm_voxel_vs_anchor"] = "the 1 - pcqm_voxel ranges of the model's and the anchor's curve do not overlap: no BD-rate"
+        except Exception as e:
+            entry["error_pcqm_voxel_vs_anchor"] = repr(e)
 out = {"rows": rows, "bjontegaard": bd,
        "note": ("weights from " + os.path.basename(sys.argv[2]) if len(sys.argv) > 2 else "seeded random weights") +
                f" (FiLM-head gain {film_gain}); synthetic shells sized like the 8iVFB frames",
        **({"anchor_rows": anchor_rows, "anchor": "octree + RAHT (pcc_amd.anchor): lossless PCO1 geometry, BT.709 YUV attributes, "
                                                   "qstep = {2, 4, 8, 16, 32, 64} / 255"} if with_anchor else {}),
        **({"target_rows": target_rows} if target_bpps else {}),
+       **({"pcqm_voxel": "PCQM's structure on the voxel grid (pcc_amd.pcqm); a stand-in, not comparable with the PCQM binary's numbers"}
+          if with_pcqm else {}),
        "rate_axis_monotone_in_q": {nm: [r["bpp"] for r in rows if r["frame"] == nm] == sorted(r["bpp"] for r in rows if r["frame"] == nm)
                                    for nm in names}}
 path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "rd_sweep.json")
