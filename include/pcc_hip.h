@@ -460,6 +460,34 @@ int pcc_octree_expand(const uint8_t* occupancy, const int64_t* level_counts, int
                       int32_t* coords_out, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Neighbour contexts of the octree coder (the opt-in stream "PCO2"; container and model in
+ * octree.py, DESIGN.md "Octree contexts (PCO2)").  The pattern of a node at level L is 6 bits,
+ * bit 0 +x, 1 -x, 2 +y, 3 -y, 4 +z, 5 -z, set when that face neighbour is an occupied node of
+ * level L; a neighbour outside [0, 2^L)^3 is absent.  Bit j of a node's occupancy byte is a
+ * binary symbol with context pattern * 8 + j (512 contexts).
+ *
+ * pcc_octree_context_levels: pcc_octree_occupancy (same arguments, same occupancy and
+ *   level_counts), and in the same layout patterns[L * n ...] = one pattern byte per node, and
+ *   hists [depth, 512, 2] uint32 (device; zeroed here) = per level the number of (context, bit)
+ *   pairs.  Integer atomics only: the histograms do not depend on the order of execution.
+ * pcc_octree_patterns: nodes = the n ascending 3*level-bit Morton keys of one level (device)
+ *   -> patterns [n].
+ * pcc_octree_expand_level: one step of pcc_octree_expand.  nodes [n] and their occupancy bytes
+ *   [n] (device) -> next [n_next], the keys (node << 3) | child of the next level, ascending.
+ *   The caller has checked that no byte is 0 and that the popcounts sum to n_next; children
+ *   past n_next are dropped, never written.  scratch: pcc_octree_scratch_bytes(n).
+ * pcc_octree_keys_to_coords: leaf keys [n] (device) -> coords_out [n,4] = (batch, x, y, z).
+ * ------------------------------------------------------------------------------------- */
+int pcc_octree_context_levels(const int32_t* coords, int64_t n, int32_t stride, const int32_t* origin,
+                              int32_t depth, uint8_t* occupancy, uint8_t* patterns, uint32_t* hists,
+                              int32_t* level_counts, void* scratch, int64_t scratch_bytes, void* stream);
+int pcc_octree_patterns(const uint64_t* nodes, int64_t n, int32_t level, uint8_t* patterns, void* stream);
+int pcc_octree_expand_level(const uint64_t* nodes, const uint8_t* occupancy, int64_t n, int64_t n_next,
+                            uint64_t* next, void* scratch, int64_t scratch_bytes, void* stream);
+int pcc_octree_keys_to_coords(const uint64_t* keys, int64_t n, int32_t stride, const int32_t* origin,
+                              int32_t batch, int32_t* coords_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Quality metrics: nearest-neighbour association on integer grids.  Replaces the open3d KD-tree
  * queries of PointCloudMetric (metrics/metric.py:36-43).  For every query row (b,x,y,z) finds the
  * nearest target voxel through the target's hash table (pcc_hash_build): nn_idx = target row,

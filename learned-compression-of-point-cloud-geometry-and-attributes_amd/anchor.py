@@ -2,7 +2,7 @@
 rate-distortion sweep to compare the learned codec against (the reference compares against MPEG's G-PCC and V-PCC binaries,
 evaluate.py:55-216 and plot.py:373-404, which are not part of its tree).  It is NOT G-PCC compatible.
 
-Geometry: lossless, the "PCO1" octree stream (octree.py).  Lossy geometry rate points come from coding a down-sampled cloud
+Geometry: lossless, the "PCO1" octree stream (octree.py), or with ``contexts=True`` its neighbour-context form "PCO2".  Lossy geometry rate points come from coding a down-sampled cloud
 (voxelize.downsample).  Attributes: RAHT coefficients quantised with one step size and range coded, "PCR1" (raht.py), by default
 in BT.709 YUV.  The RAHT plan uses the origin and depth of the PCO1 header, so the decoder rebuilds it from the geometry alone.
 
@@ -46,16 +46,17 @@ def from_coded(values, colorspace="yuv"):
 
 
 def _geometry_header(pco1):
-    """PCO1 bytes -> (depth, (ox, oy, oz), n)"""
-    if len(pco1) < 28 or pco1[:4] != octree.MAGIC:
-        raise ValueError("PCA1: the geometry is not a PCO1 stream")
+    """PCO1 or PCO2 bytes (the same 28-byte header) -> (depth, (ox, oy, oz), n)"""
+    if len(pco1) < 28 or pco1[:4] not in (octree.MAGIC, octree.MAGIC_CONTEXTS):
+        raise ValueError("PCA1: the geometry is neither a PCO1 nor a PCO2 stream")
     depth, _, _, _, ox, oy, oz, n = struct.unpack("<BBHi3iI", pco1[4:28])
     return depth, (ox, oy, oz), n
 
 
-def compress(x, qstep, colorspace="yuv", path=None):
+def compress(x, qstep, colorspace="yuv", path=None, contexts=False):
     """x: [N,6] on the GPU (integer voxel coordinates as floats + rgb in [0, 1]; no voxel twice), ``qstep``: the quantisation
-    step of the RAHT coefficients (colour units: 1/255 is one 8-bit level) -> PCA1 bytes, also written to ``path`` if given"""
+    step of the RAHT coefficients (colour units: 1/255 is one 8-bit level) -> PCA1 bytes, also written to ``path`` if given.
+    ``contexts``: code the geometry as PCO2 (neighbour contexts) instead of PCO1; ``decompress`` reads either."""
     if colorspace not in COLORSPACES:
         raise ValueError(f"colorspace {colorspace!r}: 'yuv' or 'rgb'")
     if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
@@ -64,7 +65,7 @@ def compress(x, qstep, colorspace="yuv", path=None):
         raise ValueError(f"anchor.compress: expected a [N, 6] cloud (xyz + rgb) with N >= 1, got {tuple(x.shape)}")
     xyz = torch.round(x[:, :3]).to(torch.int32)
     coords = torch.cat([torch.zeros_like(xyz[:, :1]), xyz], dim=1).contiguous()
-    geometry = octree.encode_coordinates(coords, 1)
+    geometry = octree.encode_coordinates(coords, 1, contexts=contexts)
     depth, origin, _ = _geometry_header(geometry)
     p = raht.plan(coords, origin=origin, depth=depth)
     attributes = raht.encode_attributes(p, to_coded(x[:, 3:6], colorspace), qstep)

@@ -120,12 +120,12 @@ def _pcqm_columns(metric):
     return {k: v for k, v in res.items() if k.startswith("pcqm_")}
 
 
-def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, colorspace="yuv", pcqm=False):
+def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, colorspace="yuv", pcqm=False, contexts=False):
     """one row of the sweep table for the octree + RAHT anchor codec (anchor.py) at quantisation step ``qstep``: the keys of
     ``evaluate_frame``'s row without the quality-map pair, plus ``qstep`` and ``codec``.  ``bpp`` counts the whole PCA1 stream;
     the geometry is lossless, so ``sym_p2p_psnr`` is inf and ``n_decoded`` equals ``n_source``.  ``downsample`` and
     ``resolution`` mean what they mean in ``evaluate_frame``: the anchor's lossy-geometry rate points are coarser grids; so does
-    ``pcqm``."""
+    ``pcqm``.  ``contexts``: the anchor's geometry as PCO2 (octree.py: neighbour contexts) instead of PCO1."""
     from . import anchor
     n_input = None
     if downsample is not None:
@@ -140,7 +140,7 @@ def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, color
 
     torch.cuda.synchronize()
     t0 = time.time()
-    stream = anchor.compress(src, qstep, colorspace=colorspace)
+    stream = anchor.compress(src, qstep, colorspace=colorspace, contexts=contexts)
     torch.cuda.synchronize()
     t_c = time.time() - t0
 

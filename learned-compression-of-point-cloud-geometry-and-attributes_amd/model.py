@@ -9,6 +9,7 @@ stride-8 latent coordinates (model/model.py:318-395); that binary is external an
 (model/model.py:241-256); the coordinate payload is written by the build's own lossless octree
 coder (octree.py + csrc/octree.hip, "PCO1"), which is NOT G-PCC-compatible.
 """
+import os
 import struct
 
 import torch
@@ -36,6 +37,10 @@ class ColorModel(nn.Module):
         else:
             self.entropy_model = MeanScaleHyperprior_Map(config["entropy_model"])
             self.entropy_model_map = None
+        # the stream format gpcc_encode writes: "pco1" (octree.py, the default) or "pco2" (neighbour contexts); PCC_COORD_CODER
+        self.coord_coder = os.environ.get("PCC_COORD_CODER", "pco1").lower()
+        if self.coord_coder not in ("pco1", "pco2"):
+            raise ValueError(f"PCC_COORD_CODER={self.coord_coder!r}: 'pco1' or 'pco2'")
 
     # -- model/model.py:30-47 ------------------------------------------------------------------
     def update(self, force=True):
@@ -198,8 +203,11 @@ class ColorModel(nn.Module):
     # -- container (model/model.py:214-315) --------------------------------------------------------------
     def gpcc_encode(self, points, directory=None):
         """model/model.py:318-364: latent coordinates [N,4] -> bytes.  ``directory`` (the reference's
-        scratch location for tmc3's temporary files) is accepted and unused: nothing touches disk."""
-        return octree.encode_coordinates(points, self.LATENT_STRIDE)
+        scratch location for tmc3's temporary files) is accepted and unused: nothing touches disk.
+        ``self.coord_coder`` picks the stream format; gpcc_decode reads either."""
+        if self.coord_coder not in ("pco1", "pco2"):
+            raise ValueError(f"coord_coder {self.coord_coder!r}: 'pco1' or 'pco2'")
+        return octree.encode_coordinates(points, self.LATENT_STRIDE, contexts=self.coord_coder == "pco2")
 
     def gpcc_decode(self, bin, directory=None):
         """model/model.py:366-395: bytes -> float64 [N,3] like the reference's PLY read-back (on the

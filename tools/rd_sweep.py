@@ -6,7 +6,7 @@ Seeded random weights in their q-RESPONSIVE variant (synthetic.FILM_GAIN_Q_RESPO
 follows the quality map; PCC_SWEEP_FILM_GAIN overrides): the rate axis is a real sweep, the distortion axis is that of random
 weights — not codec quality.
 
-usage: rd_sweep.py [--d2 R] [--pcqm] [--downsample F] [--anchor] [--target-bpp B [B ...]] [out.json] [weights.pt]
+usage: rd_sweep.py [--d2 R] [--pcqm] [--downsample F] [--anchor] [--anchor-contexts] [--target-bpp B [B ...]] [out.json] [weights.pt]
   --d2 R: add the point-to-plane PSNR, normals over R voxels
   --pcqm: add ``pcqm_voxel`` (pcc_amd.pcqm: PCQM's structure on the voxel grid, a stand-in that is NOT comparable with the numbers
           of the PCQM binary behind the reference's ``pcqm`` column) and its pooled features to every row; with --anchor also the
@@ -15,6 +15,7 @@ usage: rd_sweep.py [--d2 R] [--pcqm] [--downsample F] [--anchor] [--target-bpp B
                   are 1, 2, 4, 8), metrics against the down-sampled source
   --anchor: also code every frame with the octree + RAHT anchor codec (pcc_amd.anchor) at qstep = {2, 4, 8, 16, 32, 64} / 255 and
             report the model's BD-rate and BD-PSNR (Y) against the anchor's curve of the same frame
+  --anchor-contexts: --anchor with the anchor's geometry coded as PCO2 (pcc_amd.octree: neighbour contexts) instead of PCO1
   --target-bpp B [B ...]: add rows coded to a target instead of a q pair (pcc_amd.rate_control.compress_to_target: the y + z payload
             in bits per input point stays at or below B); each row is the frame evaluated at the (q_g, q_a) the search chose, with
             the target, the probe count and whether it was reached ("target_rows" of the output; the q-grid rows are unchanged)"""
@@ -41,8 +42,11 @@ if "--downsample" in sys.argv:
     at = sys.argv.index("--downsample")
     downsample = float(sys.argv[at + 1])
     del sys.argv[at:at + 2]
-with_anchor = "--anchor" in sys.argv
-if with_anchor:
+anchor_contexts = "--anchor-contexts" in sys.argv
+if anchor_contexts:
+    sys.argv.remove("--anchor-contexts")
+with_anchor = anchor_contexts or "--anchor" in sys.argv
+if "--anchor" in sys.argv:
     sys.argv.remove("--anchor")
 target_bpps = []
 if "--target-bpp" in sys.argv:
@@ -94,7 +98,7 @@ with tempfile.TemporaryDirectory() as td:
                   f"(row {time.time()-t0:.1f} s)", flush=True)
         for qstep in (ANCHOR_QSTEPS if with_anchor else ()):
             t0 = time.time()
-            row = evaluate_anchor(data, qstep, dev, downsample=downsample, pcqm=with_pcqm)
+            row = evaluate_anchor(data, qstep, dev, downsample=downsample, pcqm=with_pcqm, contexts=anchor_contexts)
             row["frame"] = name
             anchor_rows.append(row)
             print(f"{name:13s} N={row['n_source']:8d} anchor qstep {qstep * 255:.0f}/255 bpp {row['bpp']:.3f} Y {row['sym_y_psnr']:.2f} "
@@ -143,7 +147,7 @@ for nm in (names if with_anchor else ()):
 out = {"rows": rows, "bjontegaard": bd,
        "note": ("weights from " + os.path.basename(sys.argv[2]) if len(sys.argv) > 2 else "seeded random weights") +
                f" (FiLM-head gain {film_gain}); synthetic shells sized like the 8iVFB frames",
-       **({"anchor_rows": anchor_rows, "anchor": "octree + RAHT (pcc_amd.anchor): lossless PCO1 geometry, BT.709 YUV attributes, "
+       **({"anchor_rows": anchor_rows, "anchor": "octree + RAHT (pcc_amd.anchor): lossless " + ("PCO2" if anchor_contexts else "PCO1") + " geometry, BT.709 YUV attributes, "
                                                   "qstep = {2, 4, 8, 16, 32, 64} / 255"} if with_anchor else {}),
        **({"target_rows": target_rows} if target_bpps else {}),
        **({"pcqm_voxel": "PCQM's structure on the voxel grid (pcc_amd.pcqm); a stand-in, not comparable with the PCQM binary's numbers"}
