@@ -172,6 +172,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ constexpr int mfma32_row(int reg) { return (reg & 3) + 8 * (reg >> 2); }
 
+// ---- LDS-DMA through a raw buffer resource (buffer_load ... lds; conv.hip and conv_bwd.hip)
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+constexpr uint32_t BUF_OOB = 0xFFFFF000u;       // voffset of lanes that must read zeros (>= num_records)
+constexpr uint32_t BUF_FLAGS = 0x00020000u;     // raw buffer, 32-bit elements (gfx9 family word 3)
+
 // One-workgroup forms of the small per-map chains (bit 0: execution order <= 16,384 rows, bit 1: top-k <= 32,768 rows, bit 2:
 // coordinate sets <= 8,192 candidates): on unless PCC_ORDER_SMALL=0 / PCC_TOPK_SMALL=0 / PCC_UNIQUE_SMALL=0, or switched at run
 // time through pcc_small_paths (coords.hip; A/B measurements in one process).

@@ -146,7 +146,6 @@ constexpr int conv_lds_bytes() { return 2 * (BM * A_LD_DMA + (X3 ? 12 : 8) * BN 
 // 1 KB of zeros: the gather source of absent neighbours on the LDS-DMA path
 __device__ float g_zero_line[256] = {0.0f};   // cin <= 256: the per-step channel offset stays inside
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
 // ---- the pieces conv_mfma_kernel and conv_mfma_buf_kernel are both built from (BM x BN output tile, four waves, each
@@ -465,9 +464,6 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
 // Limits: fin, nbr and the packed weights must each be < 4 GiB (32-bit buffer offsets); larger
 // operands take conv_mfma_kernel.
 // ---------------------------------------------------------------------------------------------
-constexpr uint32_t BUF_OOB = 0xFFFFF000u;       // voffset of lanes that must read zeros (>= num_records)
-[[maybe_unused]] constexpr uint32_t BUF_FLAGS = 0x00020000u;     // raw buffer, 32-bit elements (gfx9 family word 3)
-
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (I < N) {

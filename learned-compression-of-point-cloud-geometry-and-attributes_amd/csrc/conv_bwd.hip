@@ -19,17 +19,15 @@
 // Roofline: MFMA fp32; algorithmic FLOPs = 2 * pairs * cin * cout, like the forward.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace pcc {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 constexpr int WG_SPLIT_MAX = 128;     // row-group splits per (offset, weight block): the grid must be many times the chip
                                       // (256 CUs x 5 workgroups) because offsets differ 3x in pair count (the centre has them all)
 constexpr int WG_SPLIT_THIN = 256;     // the scalar kernel walks its rows serially: many short walks
-constexpr uint32_t WG_OOB = 0xFFFFF000u;
-[[maybe_unused]] constexpr uint32_t WG_FLAGS = 0x00020000u;
 
 __global__ __launch_bounds__(256) void map_transpose_kernel(const int32_t* __restrict__ nbr, int64_t n_out, int K,
                                                             int32_t* __restrict__ nbr_t, uint32_t* __restrict__ mask_t) {
@@ -73,14 +71,84 @@ __device__ __forceinline__ void store_partial_tile(const f32x16& acc, float* P, 
     for (int reg = 0; reg < 16; ++reg) p[(int64_t)mfma32_row(reg) * cout] = acc[reg];
 }
 
+// ---- the pieces the four MFMA weight-gradient kernels share ----
+
+// Roles of a thread in its 256-thread workgroup
+struct WgradRoles {
+    int lane, wave_u;     // lane of the wave; wave of the workgroup (wave-uniform)
+    int r, h;             // MFMA role: lane (r, h) of the 32 x 32 tile (mfma32_row, common.h)
+    int slot, rsub;       // DMA role: 8 lanes per row (16 bytes each), 8 rows per instruction
+    int64_t ng;           // groups of 32 output rows
+};
+__device__ __forceinline__ WgradRoles wgrad_roles(int64_t n_out) {
+    const int t = threadIdx.x, lane = t & 63;
+    return {lane, __builtin_amdgcn_readfirstlane(t >> 6), lane & 31, lane >> 5, lane & 7, lane >> 3, (n_out + 31) >> 5};
+}
+
+// Buffer resource over a [rows][width] tensor: a voffset of BUF_OOB (any offset past the tensor) reads zeros
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wgrad_rsrc(const float* p, int64_t rows, int width, int elem_bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, (int)(uint32_t)(rows * width * elem_bytes), BUF_FLAGS);
+}
+// Where this lane's 16 bytes of a row start (col_byte: the chunk's first column + the lane's slot, in bytes); zeros for an
+// absent row or chunk
+__device__ __forceinline__ uint32_t row_voffset(uint32_t row, bool present, uint32_t row_bytes, uint32_t col_byte) {
+    return present ? row * row_bytes + col_byte : BUF_OOB;
+}
+// 16 bytes per lane into the LDS image at `lds_dst` (wave-uniform; lane l lands at byte 16 l): 8 rows of 128 B per instruction
+__device__ __forceinline__ void stage16(__amdgpu_buffer_rsrc_t rsrc, const void* lds_dst, uint32_t voffset) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)lds_dst, 16, voffset, 0, 0, 0);
+}
+
+// The groups of a workgroup: s, s + SPLIT, ... in ascending order, of which only those whose mask holds one of the
+// offsets in `want` are visited.  MASKS_PER_LOAD of their masks are inspected per load (one per lane) and balloted: a
+// dependent scalar load per skipped group would cost ~1 us each.  A null gmask counts as all ones.
+struct WgradWalk {
+    static constexpr int MASKS_PER_LOAD = 64;
+    const uint32_t* gmask;
+    int64_t ng, gb;
+    int split, lane;
+    uint32_t want, gml;
+    unsigned long long todo;
+    __device__ __forceinline__ WgradWalk(const uint32_t* gmask_, int64_t ng_, int s, int split_, uint32_t offset_mask)
+        : gmask(gmask_), ng(ng_), gb((int64_t)s - MASKS_PER_LOAD * (int64_t)split_), split(split_), lane(threadIdx.x & 63),
+          want(offset_mask), gml(0u), todo(0ull) {}
+    // once the loaded masks are used up (more() is false): the next MASKS_PER_LOAD masks, unless the groups are at_end()
+    __device__ __forceinline__ void load() {
+        gb += MASKS_PER_LOAD * (int64_t)split;
+        if (at_end()) return;
+        const int64_t gmine = gb + (int64_t)lane * split;
+        gml = (gmine < ng) ? (gmask ? gmask[gmine] : 0xffffffffu) : 0u;
+        todo = __ballot((gml & want) != 0u);
+    }
+    __device__ __forceinline__ bool at_end() const { return gb >= ng; }
+    __device__ __forceinline__ bool more() const { return todo != 0ull; }
+    // while more(): the next group and the offsets of `want` it holds (the same value in every lane)
+    __device__ __forceinline__ void pop(int64_t& g, uint32_t& live) {
+        const int bit = __ffsll(todo) - 1;
+        todo &= todo - 1;
+        g = gb + (int64_t)bit * split;
+        live = (uint32_t)__shfl((int)gml, bit, 64) & want;
+    }
+    // All of it, for the kernels that fetch a group ahead; false, -1 and 0 when there is no further group.  The bf16 kernels
+    // spell the two loops out, `for (load(); !at_end(); load()) while (more()) pop`: with the result of a call that changes the
+    // walk as the condition of a loop around their MFMAs, hipcc keeps a second copy of every accumulator.
+    __device__ __forceinline__ bool next(int64_t& g, uint32_t& live) {
+        while (!more()) {
+            load();
+            if (at_end()) { g = -1; live = 0u; return false; }
+        }
+        pop(g, live);
+        return true;
+    }
+};
+
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                // [4 chunks][32 rows][32 ch]
     float* Bs = smem + 4 * 1024;     // [4 chunks][32 rows][32 co]
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wid);
+    const WgradRoles me = wgrad_roles(a.n_out);
+    const int wave_u = me.wave_u;
     const int SPLIT = a.split;
     const int k = wgrad_offset_of(blockIdx.x / SPLIT, a.K), s = blockIdx.x % SPLIT;
     const int cin0 = blockIdx.y * 128, cout0 = blockIdx.z * 128;
@@ -97,34 +165,17 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
 
     f32x16 acc[2][2] = {};
 
-    __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.fin), 0, (int)(uint32_t)(a.n_in * a.cin * 4), WG_FLAGS);
-    __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0, (int)(uint32_t)(a.n_out * a.cout * 4), WG_FLAGS);
-    const int64_t ng = (a.n_out + 31) >> 5;
-    const int slot = lane & 7, rsub = lane >> 3;          // DMA role: 8 lanes per row, 8 rows per instruction
+    const __amdgpu_buffer_rsrc_t rsrc_x = wgrad_rsrc(a.fin, a.n_in, a.cin, 4), rsrc_y = wgrad_rsrc(a.dy, a.n_out, a.cout, 4);
     const bool live_m[2] = {2 * wm < cbi, 2 * wm + 1 < cbi};
     const bool live_n[2] = {2 * wn < cbo, 2 * wn + 1 < cbo};
 
-    // my groups are s, s + SPLIT, ...; 64 of their masks are inspected per load (one per lane) and only the
-    // groups that hold offset k are visited: a dependent scalar load per skipped group would cost ~1 us each
-    int64_t gb = (int64_t)s - 64 * (int64_t)SPLIT;
-    unsigned long long live = 0ull;
-    auto pop = [&]() -> int64_t {                          // next of my groups that holds offset k, or -1
-        while (!live) {
-            gb += 64 * (int64_t)SPLIT;
-            if (gb >= ng) return -1;
-            const int64_t gmine = gb + (int64_t)lane * SPLIT;
-            const uint32_t gml = (gmine < ng) ? (a.gmask ? a.gmask[gmine] : 0xffffffffu) : 0u;
-            live = __ballot((gml >> k) & 1u);
-        }
-        const int bit = __ffsll(live) - 1;
-        live &= live - 1;
-        return gb + (int64_t)bit * SPLIT;
-    };
+    WgradWalk walk(a.gmask, me.ng, s, SPLIT, 1u << k);
     auto take = [&](bool& any) -> int64_t {                // this wave's group of the next iteration
-        int64_t g = pop();
-        any = g >= 0;
+        int64_t g, g2 = -1;
+        uint32_t one;                                      // 1u << k: nothing to choose from
+        any = walk.next(g, one);
         if (rowsplit) {                                    // second group of the iteration (or none: zero images)
-            const int64_t g2 = any ? pop() : -1;
+            if (any) walk.next(g2, one);
             if (wave_u >= 2) g = g2;
         }
         return g;
@@ -137,7 +188,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
     auto load_rows = [&](int64_t g) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int64_t pos = g * 32 + 8 * i + rsub;
+            const int64_t pos = g * 32 + 8 * i + me.rsub;
             okr[i] = g >= 0 && pos < a.n_out;
             idx[i] = okr[i] ? a.nbr[pos * a.K + k] : -1;
             row[i] = okr[i] ? (a.order ? a.order[pos] : pos) : 0;
@@ -151,19 +202,19 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
         uint32_t voa[4], vob[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            voa[i] = (idx[i] >= 0 && cw < cbi) ? (uint32_t)idx[i] * (uint32_t)(a.cin * 4) + (uint32_t)((cin0 + cw * 32) * 4 + slot * 16) : WG_OOB;
-            vob[i] = (okr[i] && cw < cbo) ? (uint32_t)row[i] * (uint32_t)(a.cout * 4) + (uint32_t)((cout0 + cw * 32) * 4 + slot * 16) : WG_OOB;
+            voa[i] = row_voffset(idx[i], idx[i] >= 0 && cw < cbi, a.cin * 4, (cin0 + cw * 32) * 4 + me.slot * 16);
+            vob[i] = row_voffset(row[i], okr[i] && cw < cbo, a.cout * 4, (cout0 + cw * 32) * 4 + me.slot * 16);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr_t)(As + wave_u * 1024 + i * 256), 16, voa[i], 0, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_y, (lds_ptr_t)(Bs + wave_u * 1024 + i * 256), 16, vob[i], 0, 0, 0);
+            stage16(rsrc_x, As + wave_u * 1024 + i * 256, voa[i]);
+            stage16(rsrc_y, Bs + wave_u * 1024 + i * 256, vob[i]);
         }
         g = take(any);
         load_rows(g);
         __syncthreads();
-        const float* Ab = As + slotA * 1024 + h * 32 + r;
-        const float* Bb = Bs + slotB * 1024 + h * 32 + r;
+        const float* Ab = As + slotA * 1024 + me.h * 32 + me.r;
+        const float* Bb = Bs + slotB * 1024 + me.h * 32 + me.r;
         for (int kp = kp0; kp < kp1; ++kp) {
             float av[2], bv[2];
 #pragma unroll
@@ -185,7 +236,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
             if (!live_n[n]) continue;
-            store_partial_tile(acc[m][n], P, a.cout, cin0 + (2 * wm + m) * 32, cout0 + (2 * wn + n) * 32 + r, h);
+            store_partial_tile(acc[m][n], P, a.cout, cin0 + (2 * wm + m) * 32, cout0 + (2 * wn + n) * 32 + me.r, me.h);
         }
     }
 #endif
@@ -214,29 +265,22 @@ __global__ __launch_bounds__(256) void conv_wgrad_slice_kernel(const WgradArgs a
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Xs = smem;                 // [NB][2 chunks][32 rows][32 ch]
     float* Ys = smem + NB * 2048;     // [NB][2 chunks][32 rows][32 co]
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wid);
+    const WgradRoles me = wgrad_roles(a.n_out);
     const int SPLIT = a.split;
     const int set = blockIdx.x / SPLIT, s = blockIdx.x % SPLIT;
     const int k0 = set * O;
-    const uint32_t set_mask = (((1u << O) - 1u) << k0) & 0x7FFFFFFu;
+    const uint32_t set_mask = (((1u << O) - 1u) << k0) & ((1u << a.K) - 1u);
     const int cbi = a.cin / 32, cbo = a.cout / 32;
-    const int tm = wave_u >> 1, tn = wave_u & 1;                  // my 32 x 32 tile of W[k]
+    const int tm = me.wave_u >> 1, tn = me.wave_u & 1;            // my 32 x 32 tile of W[k]
     const bool tile_live = tm < cbi && tn < cbo;
-    const int cw = wave_u & 1, rh = wave_u >> 1;                  // my DMA role: chunk cw, rows 16 rh .. 16 rh + 15
+    const int cw = me.wave_u & 1, rh = me.wave_u >> 1;            // my DMA role: chunk cw, rows 16 rh .. 16 rh + 15
 
     f32x16 acc[O] = {};
 
-    __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.fin), 0, (int)(uint32_t)(a.n_in * a.cin * 4), WG_FLAGS);
-    __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0, (int)(uint32_t)(a.n_out * a.cout * 4), WG_FLAGS);
-    const int64_t ng = (a.n_out + 31) >> 5;
-    const int slot = lane & 7, rsub = lane >> 3;
+    const __amdgpu_buffer_rsrc_t rsrc_x = wgrad_rsrc(a.fin, a.n_in, a.cin, 4), rsrc_y = wgrad_rsrc(a.dy, a.n_out, a.cout, 4);
 
     // ---- step iterator: (group, offset) pairs of my groups, groups ascending, offsets ascending inside a group --------
-    int64_t gb = (int64_t)s - 64 * (int64_t)SPLIT;
-    unsigned long long glive = 0ull;
-    uint32_t gml = 0u;
+    WgradWalk walk(a.gmask, me.ng, s, SPLIT, set_mask);
     int64_t it_g = -1;            // group of the pending offsets
     uint32_t it_rem = 0u;         // offsets of it_g not handed out yet
     int it_ysel = NB - 1;         // dY image of it_g (advances per group)
@@ -245,17 +289,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_slice_kernel(const WgradArgs a
         Step st;
         st.first = false;
         if (it_rem == 0u) {
-            while (!glive) {
-                gb += 64 * (int64_t)SPLIT;
-                if (gb >= ng) { st.g = -1; st.o = k0; st.ysel = 0; st.valid = false; return st; }
-                const int64_t gmine = gb + (int64_t)lane * SPLIT;
-                gml = (gmine < ng) ? (a.gmask ? a.gmask[gmine] : 0xffffffffu) : 0u;
-                glive = __ballot((gml & set_mask) != 0u);
-            }
-            const int bit = __ffsll(glive) - 1;
-            glive &= glive - 1;
-            it_g = gb + (int64_t)bit * SPLIT;
-            it_rem = (uint32_t)__shfl((int)gml, bit, 64) & set_mask;
+            if (!walk.next(it_g, it_rem)) { st.g = -1; st.o = k0; st.ysel = 0; st.valid = false; return st; }
             it_ysel = (it_ysel + 1 == NB) ? 0 : it_ysel + 1;
             st.first = true;
         }
@@ -275,7 +309,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_slice_kernel(const WgradArgs a
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int64_t pos = st.g * 32 + 16 * rh + 8 * i + rsub;
+            const int64_t pos = st.g * 32 + 16 * rh + 8 * i + me.rsub;
             const bool ok = pos < a.n_out;
             const int64_t pc = ok ? pos : a.n_out - 1;
             const int v = a.nbr[pc * a.K + st.o];
@@ -290,22 +324,20 @@ __global__ __launch_bounds__(256) void conv_wgrad_slice_kernel(const WgradArgs a
     auto issue = [&](const Step& st, int xbuf, const int (&idx)[2], const int (&yrow)[2]) {
         if (!st.valid) return;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const uint32_t vo = (idx[i] >= 0 && cw < cbi) ? (uint32_t)idx[i] * (uint32_t)(a.cin * 4) + (uint32_t)(cw * 128 + slot * 16) : WG_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr_t)(Xs + xbuf * 2048 + cw * 1024 + (16 * rh + 8 * i) * 32), 16, vo, 0, 0, 0);
-        }
+        for (int i = 0; i < 2; ++i)
+            stage16(rsrc_x, Xs + xbuf * 2048 + cw * 1024 + (16 * rh + 8 * i) * 32,
+                    row_voffset(idx[i], idx[i] >= 0 && cw < cbi, a.cin * 4, cw * 128 + me.slot * 16));
         if (st.first) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const uint32_t vo = (yrow[i] >= 0 && cw < cbo) ? (uint32_t)yrow[i] * (uint32_t)(a.cout * 4) + (uint32_t)(cw * 128 + slot * 16) : WG_OOB;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_y, (lds_ptr_t)(Ys + st.ysel * 2048 + cw * 1024 + (16 * rh + 8 * i) * 32), 16, vo, 0, 0, 0);
-            }
+            for (int i = 0; i < 2; ++i)
+                stage16(rsrc_y, Ys + st.ysel * 2048 + cw * 1024 + (16 * rh + 8 * i) * 32,
+                        row_voffset(yrow[i], yrow[i] >= 0 && cw < cbo, a.cout * 4, cw * 128 + me.slot * 16));
         }
     };
     auto compute = [&](const Step& st, int xbuf) {
         if (!tile_live) return;
-        const float* Ab = Xs + xbuf * 2048 + tm * 1024 + h * 32 + r;
-        const float* Bb = Ys + st.ysel * 2048 + tn * 1024 + h * 32 + r;
+        const float* Ab = Xs + xbuf * 2048 + tm * 1024 + me.h * 32 + me.r;
+        const float* Bb = Ys + st.ysel * 2048 + tn * 1024 + me.h * 32 + me.r;
         const int oi = st.o - k0;
 #define PCC_WG_CASE(I)                                                                                              \
     case I: {                                                                                                       \
@@ -374,7 +406,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_slice_kernel(const WgradArgs a
 #pragma unroll
     for (int o = 0; o < O; ++o) {
         if (k0 + o >= a.K) break;
-        store_partial_tile(acc[o], a.partial + ((int64_t)s * a.K + (k0 + o)) * a.cin * a.cout, a.cout, tm * 32, tn * 32 + r, h);
+        store_partial_tile(acc[o], a.partial + ((int64_t)s * a.K + (k0 + o)) * a.cin * a.cout, a.cout, tm * 32, tn * 32 + me.r, me.h);
     }
 #endif
 }
@@ -403,15 +435,16 @@ __device__ __forceinline__ bf16x8 tr_operand(const unsigned short* p) {
     const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);
 }
+// transposing read: my address inside a 4-row x 16-column block, and the block's first column within the tile
+__device__ __forceinline__ int tr_lane_offset(int lane) { return (((lane & 15) >> 2) * 64) + 16 * ((lane >> 4) & 1) + 4 * (lane & 3); }
 
 __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const WgradArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     unsigned short* As = reinterpret_cast<unsigned short*>(smem);             // [2 chunks][32 rows][64 ch]
     unsigned short* Bs = As + 2 * 2048;                                       // [2 chunks][32 rows][64 co]
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wid);
+    const WgradRoles me = wgrad_roles(a.n_out);
+    const int wave_u = me.wave_u;
     const int SPLIT = a.split;
     const int k = wgrad_offset_of(blockIdx.x / SPLIT, a.K), s = blockIdx.x % SPLIT;
     const int cin0 = blockIdx.y * 128, cout0 = blockIdx.z * 128;
@@ -423,18 +456,14 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const WgradArgs a)
 
     f32x16 acc[4] = {};
 
-    __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.fin), 0, (int)(uint32_t)(a.n_in * a.cin * 2), WG_FLAGS);
-    __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0, (int)(uint32_t)(a.n_out * a.cout * 2), WG_FLAGS);
-    const int64_t ng = (a.n_out + 31) >> 5;
-    const int slot = lane & 7, rsub = lane >> 3;
+    const __amdgpu_buffer_rsrc_t rsrc_x = wgrad_rsrc(a.fin, a.n_in, a.cin, 2), rsrc_y = wgrad_rsrc(a.dy, a.n_out, a.cout, 2);
     // staging roles: waves 0-1 the X chunks 0-1, waves 2-3 the dY chunks 0-1
     const bool stage_x = wave_u < 2;
     const int cw = wave_u & 1;
     // my tiles: t = wave, wave + 4, ...; tile t -> (m = t / TN, n = t % TN)
     int tm[4], tn[4];
     bool live[4];
-    // transposing read: my address inside a 4-row x 16-column block, and the block's first column within the tile
-    const int tr_off = (((lane & 15) >> 2) * 64) + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    const int tr_off = tr_lane_offset(me.lane);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int tt = wave_u + 4 * i;
@@ -443,49 +472,43 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const WgradArgs a)
         tn[i] = live[i] ? tt % TN : 0;
     }
 
-    for (int64_t gbase = s; gbase < ng; gbase += 64 * SPLIT) {
-      const int64_t gmine = gbase + (int64_t)lane * SPLIT;
-      const uint32_t gml = (gmine < ng) ? (a.gmask ? a.gmask[gmine] : 0xffffffffu) : 0u;
-      unsigned long long todo = __ballot((gml >> k) & 1u);
-      while (todo) {
-        const int bit = __ffsll(todo) - 1;
-        todo &= todo - 1;
-        int64_t g = gbase + (int64_t)bit * SPLIT;
+    WgradWalk walk(a.gmask, me.ng, s, SPLIT, 1u << k);
+    int64_t g;
+    uint32_t one;                                              // 1u << k: nothing to choose from
+    for (walk.load(); !walk.at_end(); walk.load()) while (walk.more()) {
+        walk.pop(g, one);
         bool second = false;
         if (two_groups) {
             int64_t g2 = -1;
-            if (todo) {
-                g2 = gbase + (int64_t)(__ffsll(todo) - 1) * SPLIT;
-                todo &= todo - 1;
-            }
-            second = g2 >= 0;
-            if (cw == 1) g = g2;                           // waves 1 and 3 stage the second group (chunk 0 of it)
+            second = walk.more();
+            if (second) walk.pop(g2, one);
+            if (cw == 1) g = g2;                           // waves 1 and 3 stage the second group (chunk 0 of it), or zeros
         }
         const int chunk = two_groups ? 0 : cw;
         uint32_t vo[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int64_t pos = g * 32 + 8 * i + rsub;
+            const int64_t pos = g * 32 + 8 * i + me.rsub;
             const bool ok = g >= 0 && pos < a.n_out;
             if (stage_x) {
                 const int idx = ok ? a.nbr[pos * a.K + k] : -1;
-                vo[i] = (idx >= 0 && chunk < cbi) ? (uint32_t)idx * (uint32_t)(a.cin * 2) + (uint32_t)((cin0 + chunk * 64) * 2 + slot * 16) : WG_OOB;
+                vo[i] = row_voffset(idx, idx >= 0 && chunk < cbi, a.cin * 2, (cin0 + chunk * 64) * 2 + me.slot * 16);
             } else {
                 const int64_t row = ok ? (a.order ? a.order[pos] : pos) : 0;
-                vo[i] = (ok && chunk < cbo) ? (uint32_t)row * (uint32_t)(a.cout * 2) + (uint32_t)((cout0 + chunk * 64) * 2 + slot * 16) : WG_OOB;
+                vo[i] = row_voffset(row, ok && chunk < cbo, a.cout * 2, (cout0 + chunk * 64) * 2 + me.slot * 16);
             }
         }
         unsigned short* dst = (stage_x ? As : Bs) + cw * 2048;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            if (stage_x) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr_t)(dst + i * 512), 16, vo[i], 0, 0, 0);
-            else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_y, (lds_ptr_t)(dst + i * 512), 16, vo[i], 0, 0, 0);
+            if (stage_x) stage16(rsrc_x, dst + i * 512, vo[i]);
+            else stage16(rsrc_y, dst + i * 512, vo[i]);
         }
         __syncthreads();
         const int nks = (two_groups && second) ? 4 : 2;
         for (int ks4 = 0; ks4 < nks; ++ks4) {                  // rows 16 ks + 8 h + j of group slot gs
             const int ks = ks4 & 1, gs = ks4 >> 1;
-            const int row0 = 16 * ks + 8 * h;                   // first of my 8 rows (k-values) in this MFMA step
+            const int row0 = 16 * ks + 8 * me.h;                // first of my 8 rows (k-values) in this MFMA step
             bf16x8 bop;
             int bn_loaded = -1;
 #pragma unroll
@@ -500,14 +523,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const WgradArgs a)
             }
         }
         __syncthreads();
-      }
     }
 
     float* P = a.partial + ((int64_t)s * a.K + k) * a.cin * a.cout;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         if (!live[i]) continue;
-        store_partial_tile(acc[i], P, a.cout, cin0 + tm[i] * 32, cout0 + tn[i] * 32 + r, h);
+        store_partial_tile(acc[i], P, a.cout, cin0 + tm[i] * 32, cout0 + tn[i] * 32 + me.r, me.h);
     }
 #endif
 }
@@ -529,9 +551,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_slice_kernel(const WgradA
     extern __shared__ __attribute__((aligned(16))) float smem[];
     unsigned short* Xs = reinterpret_cast<unsigned short*>(smem);             // [O][32 rows][64 ch]
     unsigned short* Ys = Xs + O * 2048;                                       // [32 rows][64 co]
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wid);
+    const WgradRoles me = wgrad_roles(a.n_out);
+    const int wave_u = me.wave_u;
     const int SPLIT = a.split;
     const int set = blockIdx.x / SPLIT, s = blockIdx.x % SPLIT;
     const int k0 = set * O;
@@ -540,54 +561,43 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_slice_kernel(const WgradA
 
     f32x16 acc[O] = {};
 
-    __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.fin), 0, (int)(uint32_t)(a.n_in * a.cin * 2), WG_FLAGS);
-    __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0, (int)(uint32_t)(a.n_out * a.cout * 2), WG_FLAGS);
-    const int64_t ng = (a.n_out + 31) >> 5;
-    const int slot = lane & 7, rsub = lane >> 3;
-    const int tr_off = (((lane & 15) >> 2) * 64) + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    const __amdgpu_buffer_rsrc_t rsrc_x = wgrad_rsrc(a.fin, a.n_in, a.cin, 2), rsrc_y = wgrad_rsrc(a.dy, a.n_out, a.cout, 2);
+    const int tr_off = tr_lane_offset(me.lane);
 
-    for (int64_t gbase = s; gbase < ng; gbase += 64 * (int64_t)SPLIT) {
-        const int64_t gmine = gbase + (int64_t)lane * SPLIT;
-        const uint32_t gml = (gmine < ng) ? (a.gmask ? a.gmask[gmine] : 0xffffffffu) : 0u;
-        unsigned long long todo = __ballot((gml & set_mask) != 0u);
-        while (todo) {
-            const int bit = __ffsll(todo) - 1;
-            todo &= todo - 1;
-            const int64_t g = gbase + (int64_t)bit * SPLIT;
-            const uint32_t rem = (uint32_t)__builtin_amdgcn_readfirstlane((int)(((uint32_t)__shfl((int)gml, bit, 64) & set_mask) >> k0));
-            const int64_t pos = g * 32 + 8 * wave_u + rsub;
-            const bool ok = pos < a.n_out;
-            {
-                const int yrow = ok ? (a.order ? a.order[pos] : (int)pos) : -1;
-                const uint32_t vo = yrow >= 0 ? (uint32_t)yrow * (uint32_t)(a.cout * 2) + (uint32_t)(slot * 16) : WG_OOB;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_y, (lds_ptr_t)(Ys + wave_u * 512), 16, vo, 0, 0, 0);
-            }
+    WgradWalk walk(a.gmask, me.ng, s, SPLIT, set_mask);
+    int64_t g;
+    uint32_t live;
+    for (walk.load(); !walk.at_end(); walk.load()) while (walk.more()) {
+        walk.pop(g, live);
+        const uint32_t rem = (uint32_t)__builtin_amdgcn_readfirstlane((int)(live >> k0));
+        const int64_t pos = g * 32 + 8 * wave_u + me.rsub;
+        const bool ok = pos < a.n_out;
+        const int yrow = ok ? (a.order ? a.order[pos] : (int)pos) : -1;
+        stage16(rsrc_y, Ys + wave_u * 512, row_voffset(yrow, yrow >= 0, a.cout * 2, me.slot * 16));
+#pragma unroll
+        for (int o = 0; o < O; ++o) {
+            if (!((rem >> o) & 1u)) continue;
+            const int idx = ok ? a.nbr[pos * a.K + k0 + o] : -1;
+            stage16(rsrc_x, Xs + o * 2048 + wave_u * 512, row_voffset(idx, idx >= 0, a.cin * 2, me.slot * 16));
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const int row0 = 16 * ks + 8 * me.h;
+            const bf16x8 bop = tr_operand(Ys + row0 * 64 + tn * 32 + tr_off);
 #pragma unroll
             for (int o = 0; o < O; ++o) {
-                if (!((rem >> o) & 1u)) continue;
-                const int idx = ok ? a.nbr[pos * a.K + k0 + o] : -1;
-                const uint32_t vo = idx >= 0 ? (uint32_t)idx * (uint32_t)(a.cin * 2) + (uint32_t)(slot * 16) : WG_OOB;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr_t)(Xs + o * 2048 + wave_u * 512), 16, vo, 0, 0, 0);
+                if (!((rem >> o) & 1u)) continue;                       // wave-uniform: EXEC stays all ones
+                acc[o] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(Xs + o * 2048 + row0 * 64 + tm * 32 + tr_off), bop, acc[o], 0, 0, 0);
             }
-            __syncthreads();
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const int row0 = 16 * ks + 8 * h;
-                const bf16x8 bop = tr_operand(Ys + row0 * 64 + tn * 32 + tr_off);
-#pragma unroll
-                for (int o = 0; o < O; ++o) {
-                    if (!((rem >> o) & 1u)) continue;                       // wave-uniform: EXEC stays all ones
-                    acc[o] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(Xs + o * 2048 + row0 * 64 + tm * 32 + tr_off), bop, acc[o], 0, 0, 0);
-                }
-            }
-            __syncthreads();
         }
+        __syncthreads();
     }
 
 #pragma unroll
     for (int o = 0; o < O; ++o) {
         if (k0 + o >= a.K) break;
-        store_partial_tile(acc[o], a.partial + ((int64_t)s * a.K + (k0 + o)) * a.cin * a.cout, a.cout, tm * 32, tn * 32 + r, h);
+        store_partial_tile(acc[o], a.partial + ((int64_t)s * a.K + (k0 + o)) * a.cin * a.cout, a.cout, tm * 32, tn * 32 + me.r, me.h);
     }
 #endif
 }
@@ -666,6 +676,19 @@ __global__ __launch_bounds__(256) void wgrad_reduce4_kernel(const float4* __rest
     dw[e] = sum;
 }
 
+// The legal values of an A/B switch, the default first.  pick() reads the switch; dispatch() hands the matching value to `f` as
+// a compile-time constant (std::integral_constant): template instances come from the same list as the switch's legal values.
+template <int... V>
+struct Choices {
+    static int pick(const char* env_name) {
+        const char* e = getenv(env_name);
+        const int v = e ? atoi(e) : -1, all[] = {V...};
+        return ((v == V) || ...) ? v : all[0];
+    }
+    template <class F>
+    static void dispatch(int v, F&& f) { ((v == V ? f(std::integral_constant<int, V>{}) : void()), ...); }
+};
+
 }  // namespace pcc
 
 using namespace pcc;
@@ -717,84 +740,86 @@ static inline int wgrad_slice_splits(int64_t n_out) {      // three workgroup se
 //       same box: one-offset 122-124 / 129 TFLOP/s, O = 3 137 / 135 (71 registers, 7 waves per SIMD), O = 5 121 / 119 (103
 //       registers), O = 9 140 / 125 (167 registers): fewer bytes and fewer waves trade evenly
 // ---------------------------------------------------------------------------------------------
-enum WgradFamily { WGF_THIN, WGF_ONE, WGF_SLICE, WGF_BF16_ONE, WGF_BF16_SLICE };
-
-struct WgradPlan {
-    WgradFamily family;
-    int O, ahead;         // slice kernels: offsets per workgroup; fp32 slice: steps the gathers run ahead
-    int split;            // row-group splits (the thin kernel: WG_SPLIT_THIN row ranges)
-    int partials;         // images [K][cin][cout] in the scratch
-};
+using SliceO = Choices<5, 3, 4, 6, 9>;          // PCC_WGRAD_SLICE_O
+using SliceAhead = Choices<2, 1>;               // PCC_WGRAD_AHEAD
+using Bf16SliceO = Choices<3, 0, 5, 9>;         // PCC_WGRAD_BF16_SLICE_O (0: the one-offset kernel)
 
 static inline bool wgrad_slice_on() {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("PCC_WGRAD_SLICE"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on != 0;
+    static const bool on = [] { const char* e = getenv("PCC_WGRAD_SLICE"); return !(e && e[0] == '0'); }();
+    return on;
 }
-static inline int wgrad_slice_o() {
-    static int O = -1;
-    if (O < 0) {
-        const char* e = getenv("PCC_WGRAD_SLICE_O");
-        O = e ? atoi(e) : 5;
-        if (O != 3 && O != 4 && O != 6 && O != 9) O = 5;
-    }
-    return O;
-}
-static inline int wgrad_ahead() {
-    static int ahead = -1;
-    if (ahead < 0) { const char* e = getenv("PCC_WGRAD_AHEAD"); ahead = (e && e[0] == '1') ? 1 : 2; }
-    return ahead;
-}
-static inline int wgrad_bf16_slice_o() {
-    static int slice_o = -1;
-    if (slice_o < 0) {
-        const char* e = getenv("PCC_WGRAD_BF16_SLICE_O");
-        slice_o = e ? atoi(e) : 3;
-        if (slice_o != 0 && slice_o != 3 && slice_o != 5 && slice_o != 9) slice_o = 3;
-    }
-    return slice_o;
-}
-// slice kernel (O offsets per workgroup, dY rows staged once per group): the default for 64-channel-class blocks of a
-// 27-offset kernel
-static inline bool wgrad_slice(int cin, int cout, int K) { return wgrad_slice_on() && wgrad_rowsplit(cin, cout) && K == 27; }
+static inline int wgrad_slice_o() { static const int O = SliceO::pick("PCC_WGRAD_SLICE_O"); return O; }
+static inline int wgrad_ahead() { static const int ahead = SliceAhead::pick("PCC_WGRAD_AHEAD"); return ahead; }
+static inline int wgrad_bf16_slice_o() { static const int O = Bf16SliceO::pick("PCC_WGRAD_BF16_SLICE_O"); return O; }
+
+// Everything a launch needs, and its printed name
+struct WgradPlan {
+    void (*kernel)(WgradArgs);
+    dim3 grid;
+    size_t lds;           // dynamic LDS bytes
+    int split;            // row-group splits (the thin kernel: WG_SPLIT_THIN row ranges)
+    int partials;         // images [K][cin][cout] in the scratch
+    char name[48];
+};
 
 // shape checks of a launch and its plan (n_out >= 1)
 static int plan_wgrad(bool bf16, int K, int cin, int cout, int64_t n_out, WgradPlan& p) {
-    p.O = 0; p.ahead = 0;
+    // one offset and one block of up to 128 x 128 of W[k] per workgroup
+    auto one_offset = [&](void (*kernel)(WgradArgs), const char* name, size_t lds, int per_split) {
+        p.kernel = kernel;
+        p.split = wgrad_splits(n_out);
+        p.partials = p.split * per_split;
+        p.grid = dim3((unsigned)(K * p.split), (unsigned)((cin + 127) / 128), (unsigned)((cout + 127) / 128));
+        p.lds = lds;
+        snprintf(p.name, sizeof p.name, "%s", name);
+    };
+    // O offsets per workgroup, dY rows staged once per group: 64-channel-class blocks of a 27-offset kernel
+    auto slice = [&](void (*kernel)(WgradArgs), int O, size_t lds) {
+        p.kernel = kernel;
+        p.split = p.partials = wgrad_slice_splits(n_out);
+        p.grid = dim3((unsigned)((K + O - 1) / O * p.split));
+        p.lds = lds;
+    };
     if (bf16) {
         PCC_REQUIRE(K >= 1 && K <= 27, "pcc_conv_wgrad_bf16: bad K");
         PCC_REQUIRE(cin % 64 == 0 && cout % 64 == 0 && cin >= 64 && cout >= 64, "pcc_conv_wgrad_bf16: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
-        if (wgrad_bf16_slice_o() && cin == 64 && cout == 64 && K == 27) {
-            p.family = WGF_BF16_SLICE;
-            p.O = wgrad_bf16_slice_o();
-            p.split = wgrad_slice_splits(n_out);
-        } else {
-            p.family = WGF_BF16_ONE;
-            p.split = wgrad_splits(n_out);
-        }
-        p.partials = p.split;
+        one_offset(conv_wgrad_bf16_kernel, "conv_wgrad_bf16_kernel", 4 * 2048 * sizeof(unsigned short), 1);
+        if (cin == 64 && cout == 64 && K == 27)
+            Bf16SliceO::dispatch(wgrad_bf16_slice_o(), [&](auto o) {
+                constexpr int O = decltype(o)::value;
+                if constexpr (O > 0) {
+                    slice(conv_wgrad_bf16_slice_kernel<O>, O, (O + 1) * 2048 * sizeof(unsigned short));
+                    snprintf(p.name, sizeof p.name, "conv_wgrad_bf16_slice_kernel<%d>", O);
+                }
+            });
         return PCC_OK;
     }
     PCC_REQUIRE(K >= 1 && K <= 27 && cin >= 1 && cout >= 1, "pcc_conv_wgrad: bad shape");
     if (!wgrad_mfma(cin, cout)) {
         PCC_REQUIRE((int64_t)cin * cout <= 4096, "pcc_conv_wgrad: thin path handles cin * cout <= 4096 (got %d x %d)", cin, cout);
-        p.family = WGF_THIN;
+        p.kernel = conv_wgrad_thin_kernel;
         p.split = p.partials = WG_SPLIT_THIN;
-    } else if (wgrad_slice(cin, cout, K)) {
-        p.family = WGF_SLICE;
-        p.O = wgrad_slice_o();
-        p.ahead = wgrad_ahead();
-        p.split = p.partials = wgrad_slice_splits(n_out);
-    } else {
-        p.family = WGF_ONE;
-        p.split = wgrad_splits(n_out);
-        p.partials = p.split * (wgrad_rowsplit(cin, cout) ? 4 : 1);     // two row groups per iteration, one partial per wave
+        p.grid = dim3((unsigned)(K * WG_SPLIT_THIN));
+        p.lds = 0;
+        snprintf(p.name, sizeof p.name, "conv_wgrad_thin_kernel");
+    } else if (wgrad_slice_on() && wgrad_rowsplit(cin, cout) && K == 27) {
+        SliceO::dispatch(wgrad_slice_o(), [&](auto o) {
+            SliceAhead::dispatch(wgrad_ahead(), [&](auto ahead) {
+                constexpr int O = decltype(o)::value, AHEAD = decltype(ahead)::value;
+                slice(conv_wgrad_slice_kernel<O, AHEAD>, O, 2 * (AHEAD + 1) * 2048 * sizeof(float));
+                snprintf(p.name, sizeof p.name, "conv_wgrad_slice_kernel<%d, %d>", O, AHEAD);
+            });
+        });
+    } else {      // (64-channel class: two row groups per iteration, one partial per wave)
+        one_offset(conv_wgrad_kernel, "conv_wgrad_kernel", 8 * 1024 * sizeof(float), wgrad_rowsplit(cin, cout) ? 4 : 1);
     }
     return PCC_OK;
 }
 
 int64_t pcc_conv_wgrad_scratch_elems(int32_t K, int32_t cin, int32_t cout) {
-    // the largest layout any plan of the shape uses: WG_SPLIT_MAX x 4 rowsplit partials >= WG_SPLIT_SLICE_MAX slice partials
+    // the largest layout any plan of the shape uses.  64-channel class: the one-offset kernel writes a partial per wave (4 per
+    // split), the slice kernels one per split
+    static_assert(WG_SPLIT_MAX * 4 >= WG_SPLIT_SLICE_MAX, "the rowsplit layout must bound the slice layout");
     const int partials = !wgrad_mfma(cin, cout) ? WG_SPLIT_THIN : WG_SPLIT_MAX * (wgrad_rowsplit(cin, cout) ? 4 : 1);
     return (int64_t)partials * K * cin * cout;
 }
@@ -803,18 +828,11 @@ int pcc_conv_wgrad_kernel_name(int32_t bf16, int32_t K, int32_t cin, int32_t cou
                                int32_t* split, int32_t* partials) {
     WgradPlan p;
     if (int rc = plan_wgrad(bf16 != 0, K, cin, cout, n_out, p)) return rc;
-    if (n_out <= 0) { p.split = p.partials = 0; }             // no kernel: the launch zero-fills dw
+    if (n_out <= 0) { p.split = p.partials = 0; p.name[0] = 0; }      // no kernel: the launch zero-fills dw
     if (split) *split = p.split;
     if (partials) *partials = p.partials;
     if (buf == nullptr) return PCC_OK;
-    int n;
-    if (n_out <= 0) n = snprintf(buf, len, "%s", "");
-    else if (p.family == WGF_THIN) n = snprintf(buf, len, "conv_wgrad_thin_kernel");
-    else if (p.family == WGF_ONE) n = snprintf(buf, len, "conv_wgrad_kernel");
-    else if (p.family == WGF_SLICE) n = snprintf(buf, len, "conv_wgrad_slice_kernel<%d, %d>", p.O, p.ahead);
-    else if (p.family == WGF_BF16_ONE) n = snprintf(buf, len, "conv_wgrad_bf16_kernel");
-    else n = snprintf(buf, len, "conv_wgrad_bf16_slice_kernel<%d>", p.O);
-    PCC_REQUIRE(n < len, "pcc_conv_wgrad_kernel_name: %d bytes do not hold the name", len);
+    PCC_REQUIRE(snprintf(buf, len, "%s", p.name) < len, "pcc_conv_wgrad_kernel_name: %d bytes do not hold the name", len);
     return PCC_OK;
 }
 
@@ -828,7 +846,7 @@ static int wgrad(bool bf16, const float* fin, int64_t n_in, int cin, const float
     const uint64_t esz = bf16 ? 2 : 4;
     WgradPlan p;
     auto check_operands = [&]() -> int {       // what the LDS-DMA kernels need of the gathered tensors
-        PCC_REQUIRE((uint64_t)n_in * cin * esz <= WG_OOB && (uint64_t)n_out * cout * esz <= WG_OOB,
+        PCC_REQUIRE((uint64_t)n_in * cin * esz <= BUF_OOB && (uint64_t)n_out * cout * esz <= BUF_OOB,
                     "%s: operands of 4 GiB and more are not supported", who);
         PCC_REQUIRE(((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0,
                     "%s: fin and dy must be 16-byte aligned (16-byte LDS-DMA loads)", who);
@@ -853,36 +871,11 @@ static int wgrad(bool bf16, const float* fin, int64_t n_in, int cin, const float
         PCC_REQUIRE(scratch_elems >= (int64_t)p.partials * elems, "%s: scratch too small", who);
     } else {
         if (int rc = plan_wgrad(false, K, cin, cout, n_out, p)) return rc;
-        if (p.family != WGF_THIN)
+        if (p.kernel != conv_wgrad_thin_kernel)
             if (int rc = check_operands()) return rc;
     }
     const WgradArgs a = {fin, dy, nbr, order, gmask, scratch, n_in, n_out, cin, cout, K, p.split};
-    if (p.family == WGF_SLICE) {
-#define PCC_SLICE(OO)                                                                                                              \
-    do {                                                                                                                           \
-        const dim3 grid((unsigned)(((27 + OO - 1) / OO) * a.split));                                                               \
-        if (p.ahead == 1) hipLaunchKernelGGL((conv_wgrad_slice_kernel<OO, 1>), grid, dim3(256), 2 * 2 * 2048 * sizeof(float), st, a); \
-        else hipLaunchKernelGGL((conv_wgrad_slice_kernel<OO, 2>), grid, dim3(256), 2 * 3 * 2048 * sizeof(float), st, a);            \
-    } while (0)
-        if (p.O == 3) PCC_SLICE(3);
-        else if (p.O == 4) PCC_SLICE(4);
-        else if (p.O == 6) PCC_SLICE(6);
-        else if (p.O == 9) PCC_SLICE(9);
-        else PCC_SLICE(5);
-#undef PCC_SLICE
-    } else if (p.family == WGF_BF16_SLICE) {
-        const unsigned sets = (unsigned)((K + p.O - 1) / p.O);
-        const size_t lds = (size_t)(p.O + 1) * 2048 * sizeof(unsigned short);
-        if (p.O == 3) hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<3>, dim3(sets * a.split), dim3(256), lds, st, a);
-        else if (p.O == 5) hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<5>, dim3(sets * a.split), dim3(256), lds, st, a);
-        else hipLaunchKernelGGL(conv_wgrad_bf16_slice_kernel<9>, dim3(sets * a.split), dim3(256), lds, st, a);
-    } else if (p.family == WGF_THIN) {
-        hipLaunchKernelGGL(conv_wgrad_thin_kernel, dim3((unsigned)(K * WG_SPLIT_THIN)), dim3(256), 0, st, a);
-    } else {                                  // one offset and one block of up to 128 x 128 of W[k] per workgroup
-        const dim3 grid((unsigned)(K * a.split), (unsigned)((cin + 127) / 128), (unsigned)((cout + 127) / 128));
-        if (p.family == WGF_BF16_ONE) hipLaunchKernelGGL(conv_wgrad_bf16_kernel, grid, dim3(256), 4 * 2048 * sizeof(unsigned short), st, a);
-        else hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 8 * 1024 * sizeof(float), st, a);
-    }
+    hipLaunchKernelGGL(p.kernel, p.grid, dim3(256), p.lds, st, a);
     launch_wgrad_reduce(scratch, elems, p.partials, dw, st);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
