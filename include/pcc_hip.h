@@ -593,12 +593,39 @@ int pcc_pcqm_features(const int32_t* coords_r, int64_t n_r, const uint64_t* keys
  * workgroup order in scratch (pcc_image_compare_scratch_bytes(H, W) bytes; 0 for a size the call refuses); a
  * final pass adds them in ascending order.  No float atomics: bitwise reproducible.  Refused before any
  * launch: H or W below 7 or above 8192, null pointers, a short scratch.
+ *
+ * pcc_view_visibility answers "which points did that image show?" for the view pcc_render_view would draw
+ * (the same axes, framing, splat, clipping and winner rule; no colours, no image).  For every row i:
+ *   behind[i] = the minimum, over the pixels of the row's splat that lie inside the image, of
+ *               d_win(pixel) - d_i, where d_win is the largest d splatted onto the pixel.  Always >= 0; 0 exactly
+ *               when the point lies on the z-buffer front in at least one of its pixels; at most 2 *
+ *               PCC_COORD_LIMIT.  PCC_VIS_OFFSCREEN when no pixel of the splat lies inside the image, and for a
+ *               row with a coordinate beyond PCC_COORD_LIMIT (which draws nothing, as in the renderer).
+ *   won[i]    = the number of pixels whose winner is row i under the renderer's full rule (largest d, then the
+ *               lowest row index).  won[i] > 0 implies behind[i] == 0; the converse fails for a point that ties
+ *               the front depth in all its pixels but loses every tie.  `behind` does not depend on the tie
+ *               rule (it compares depths only) and so not on the row order; `won` does.
+ * accumulate != 0 folds the view into what the arrays hold: behind[i] = min(old, new), won[i] = old + new (the
+ * caller has initialised them, e.g. by a first call with accumulate == 0, which overwrites).  scratch: the
+ * z-buffer, pcc_visibility_scratch_bytes(H, W) = pcc_render_scratch_bytes(H, W) bytes (0 for a size the call
+ * refuses).  Three launches: clear, the renderer's splat, and one thread per point that walks its splat again
+ * and reads the words: that thread owns its row's outputs, so there are no atomics beyond the splat's maximum
+ * and both outputs are bitwise reproducible.  Refused before any launch (PCC_ERR_ARG) on pcc_render_view's
+ * conditions: bad axes, scale outside 1..64, point_size outside 1..16, H or W outside 1..8192, n above
+ * 2^32 - 2, a null cloud or null outputs with n > 0, a null or short z-buffer.  n == 0 is valid, launches
+ * nothing and touches no array.  Not a camera: orthographic, axis views only, square splats.
  * ------------------------------------------------------------------------------------- */
+#define PCC_VIS_OFFSCREEN 2147483647
 int64_t pcc_render_scratch_bytes(int32_t H, int32_t W);
 int pcc_render_view(const int32_t* coords, const uint8_t* rgb8, int64_t n, const int32_t* right, const int32_t* up,
                     const int32_t* front, int32_t u_min, int32_t v_max, int32_t ox, int32_t oy, int32_t scale,
                     int32_t point_size, int32_t H, int32_t W, const uint8_t* background, void* scratch,
                     int64_t scratch_bytes, uint8_t* image, void* stream);
+int64_t pcc_visibility_scratch_bytes(int32_t H, int32_t W);
+int pcc_view_visibility(const int32_t* coords, int64_t n, const int32_t* right, const int32_t* up,
+                        const int32_t* front, int32_t u_min, int32_t v_max, int32_t ox, int32_t oy, int32_t scale,
+                        int32_t point_size, int32_t H, int32_t W, void* scratch, int64_t scratch_bytes,
+                        int32_t accumulate, int32_t* behind, int32_t* won, void* stream);
 int32_t pcc_image_compare_tile(void);
 int64_t pcc_image_compare_scratch_bytes(int32_t H, int32_t W);
 int pcc_image_compare(const uint8_t* ref, const uint8_t* img, int32_t H, int32_t W, void* scratch,

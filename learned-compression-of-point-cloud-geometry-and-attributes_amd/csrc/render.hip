@@ -16,7 +16,11 @@
 // < 2^18, so d + 2^18 is positive and the word of a drawn pixel is never 0; a row with a coordinate outside the range draws
 // nothing.  Atomic bound: n point_size^2 64-bit atomics on H W words.
 //
-// pcc_image_compare replaces rgb2yuv + peak_signal_noise_ratio + structural_similarity (evaluate_view_dep.py:196-204) by
+// pcc_view_visibility is the way back from the pixels to the points: the same clear and splat, then one thread per point walks
+// its splat again and reads how far the point lies behind the z-buffer front (`behind`, the minimum over its pixels) and how
+// many pixels it owns (`won`).  No image is resolved.
+//
+// pcc_image_compare replaces rgb2yuv +peak_signal_noise_ratio + structural_similarity (evaluate_view_dep.py:196-204) by
 // their raw sums in float64: one workgroup per IC_TILE x IC_TILE tile converts the tile and its 6-pixel apron to YUV one
 // channel at a time into LDS, adds the squared differences of the pixels it owns and the SSIM map values of the 7 x 7
 // windows whose top-left pixel it owns, reduces them over a fixed tree and stores its eight partials; a second kernel
@@ -88,8 +92,49 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(const uint64_t* __r
     }
 }
 
+// ---- visibility: the way back from the z-buffer's pixels to the points ----
+// One thread per point walks the point's splat again, over the z-buffer the splat kernel has finished: behind = the smallest
+// (d of the pixel's winner) - (d of this point) over its pixels inside the image, won = the pixels whose word is this row's own.
+// Every pixel of the splat holds a word of depth >= d (this row took part in its maximum), so behind >= 0, and it is 0 exactly
+// where the front depth of a pixel is this point's; the tie to the lowest row decides only `won`.  A thread owns its row's two
+// outputs: no atomics, and `accumulate` is a plain read-modify-write (min of behind, sum of won).
+__global__ __launch_bounds__(256) void visibility_gather_kernel(const int32_t* __restrict__ coords, int64_t n, RenderView a,
+                                                                const uint64_t* __restrict__ zbuf, int accumulate,
+                                                                int32_t* __restrict__ behind, int32_t* __restrict__ won) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    const int4 c = reinterpret_cast<const int4*>(coords)[row];
+    int32_t best = PCC_VIS_OFFSCREEN, count = 0;
+    if (coord_in_range(0, c.y, c.z, c.w)) {
+        const int u = a.r[0] * c.y + a.r[1] * c.z + a.r[2] * c.w;
+        const int v = a.u[0] * c.y + a.u[1] * c.z + a.u[2] * c.w;
+        const int d = a.f[0] * c.y + a.f[1] * c.z + a.f[2] * c.w;
+        const uint64_t own = ((uint64_t)(uint32_t)(d + RENDER_DEPTH_BIAS) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)row);
+        const int64_t px0 = ((int64_t)u - a.u_min) * a.scale + a.ox, py0 = ((int64_t)a.v_max - v) * a.scale + a.oy;
+        for (int j = 0; j < a.point_size; ++j) {
+            const int64_t py = py0 + j;
+            if (py < 0 || py >= a.H) continue;
+            for (int i = 0; i < a.point_size; ++i) {
+                const int64_t px = px0 + i;
+                if (px < 0 || px >= a.W) continue;
+                const uint64_t word = zbuf[py * a.W + px];
+                const int32_t gap = (int32_t)(uint32_t)(word >> 32) - RENDER_DEPTH_BIAS - d;     // 0 .. 2 COORD_LIMIT
+                best = gap < best ? gap : best;
+                count += word == own;
+            }
+        }
+    }
+    if (accumulate) {
+        const int32_t old = behind[row];
+        best = old < best ? old : best;
+        count += won[row];
+    }
+    behind[row] = best;
+    won[row] = count;
+}
+
 // ---- image metrics ----
-constexpr int IC_TILE = 32;                   // pixels a workgroup owns per side
+constexpr int IC_TILE = 32;                  // pixels a workgroup owns per side
 constexpr int IC_WIN = 7;                     // structural_similarity's window
 constexpr int IC_SPAN = IC_TILE + IC_WIN - 1; // the tile and its apron
 constexpr int IC_THREADS = 256;
@@ -194,6 +239,31 @@ static bool signed_unit_axis(const int32_t* a) {
 }
 static int dot3(const int32_t* a, const int32_t* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
+// the checks pcc_render_view and pcc_view_visibility share: the view's axes, the splat's sizes, the image's and the cloud's
+static int check_view(const char* who, const int32_t* right, const int32_t* up, const int32_t* front, int32_t scale, int32_t point_size,
+                      int32_t H, int32_t W, int64_t n) {
+    PCC_REQUIRE(right && up && front, "%s: axes required", who);
+    PCC_REQUIRE(signed_unit_axis(right) && signed_unit_axis(up) && signed_unit_axis(front),
+                "%s: right, up and front must be signed unit coordinate axes", who);
+    PCC_REQUIRE(dot3(right, up) == 0 && dot3(up, front) == 0 && dot3(right, front) == 0, "%s: axes must be mutually orthogonal", who);
+    const int32_t cross[3] = {up[1] * front[2] - up[2] * front[1], up[2] * front[0] - up[0] * front[2], up[0] * front[1] - up[1] * front[0]};
+    PCC_REQUIRE(cross[0] == right[0] && cross[1] == right[1] && cross[2] == right[2], "%s: right must be up x front", who);
+    PCC_REQUIRE(scale >= 1 && scale <= 64, "%s: scale must be 1 .. 64 (got %d)", who, scale);
+    PCC_REQUIRE(point_size >= 1 && point_size <= 16, "%s: point_size must be 1 .. 16 (got %d)", who, point_size);
+    PCC_REQUIRE(H >= 1 && H <= RENDER_MAX_DIM && W >= 1 && W <= RENDER_MAX_DIM, "%s: H and W must be 1 .. %d (got %d x %d)", who,
+                RENDER_MAX_DIM, H, W);
+    PCC_REQUIRE(n >= 0 && n <= 0xFFFFFFFEll, "%s: 0 .. 2^32 - 2 points", who);
+    return PCC_OK;
+}
+
+static RenderView make_view(const int32_t* right, const int32_t* up, const int32_t* front, int32_t u_min, int32_t v_max, int32_t ox,
+                            int32_t oy, int32_t scale, int32_t point_size, int32_t H, int32_t W) {
+    RenderView a;
+    for (int k = 0; k < 3; ++k) { a.r[k] = right[k]; a.u[k] = up[k]; a.f[k] = front[k]; }
+    a.u_min = u_min; a.v_max = v_max; a.ox = ox; a.oy = oy; a.scale = scale; a.point_size = point_size; a.H = H; a.W = W;
+    return a;
+}
+
 }  // namespace pcc
 
 using namespace pcc;
@@ -208,23 +278,12 @@ int64_t pcc_render_scratch_bytes(int32_t H, int32_t W) {
 int pcc_render_view(const int32_t* coords, const uint8_t* rgb8, int64_t n, const int32_t* right, const int32_t* up, const int32_t* front,
                     int32_t u_min, int32_t v_max, int32_t ox, int32_t oy, int32_t scale, int32_t point_size, int32_t H, int32_t W,
                     const uint8_t* background, void* scratch, int64_t scratch_bytes, uint8_t* image, void* stream) {
-    PCC_REQUIRE(right && up && front && background, "pcc_render_view: axes and background required");
-    PCC_REQUIRE(signed_unit_axis(right) && signed_unit_axis(up) && signed_unit_axis(front),
-                "pcc_render_view: right, up and front must be signed unit coordinate axes");
-    PCC_REQUIRE(dot3(right, up) == 0 && dot3(up, front) == 0 && dot3(right, front) == 0, "pcc_render_view: axes must be mutually orthogonal");
-    const int32_t cross[3] = {up[1] * front[2] - up[2] * front[1], up[2] * front[0] - up[0] * front[2], up[0] * front[1] - up[1] * front[0]};
-    PCC_REQUIRE(cross[0] == right[0] && cross[1] == right[1] && cross[2] == right[2], "pcc_render_view: right must be up x front");
-    PCC_REQUIRE(scale >= 1 && scale <= 64, "pcc_render_view: scale must be 1 .. 64 (got %d)", scale);
-    PCC_REQUIRE(point_size >= 1 && point_size <= 16, "pcc_render_view: point_size must be 1 .. 16 (got %d)", point_size);
-    PCC_REQUIRE(H >= 1 && H <= RENDER_MAX_DIM && W >= 1 && W <= RENDER_MAX_DIM, "pcc_render_view: H and W must be 1 .. %d (got %d x %d)",
-                RENDER_MAX_DIM, H, W);
-    PCC_REQUIRE(n >= 0 && n <= 0xFFFFFFFEll, "pcc_render_view: 0 .. 2^32 - 2 points");
+    if (int rc = check_view("pcc_render_view", right, up, front, scale, point_size, H, W, n)) return rc;
+    PCC_REQUIRE(background, "pcc_render_view: background required");
     PCC_REQUIRE(n == 0 || (coords && rgb8), "pcc_render_view: null cloud with n > 0");
     PCC_REQUIRE(scratch && image, "pcc_render_view: z-buffer and image required");
     PCC_REQUIRE(scratch_bytes >= pcc_render_scratch_bytes(H, W), "pcc_render_view: scratch too small");
-    RenderView a;
-    for (int k = 0; k < 3; ++k) { a.r[k] = right[k]; a.u[k] = up[k]; a.f[k] = front[k]; }
-    a.u_min = u_min; a.v_max = v_max; a.ox = ox; a.oy = oy; a.scale = scale; a.point_size = point_size; a.H = H; a.W = W;
+    const RenderView a = make_view(right, up, front, u_min, v_max, ox, oy, scale, point_size, H, W);
     const int64_t npix = (int64_t)H * W;
     const uint32_t bg = (uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16);
     hipStream_t st = as_stream(stream);
@@ -232,6 +291,27 @@ int pcc_render_view(const int32_t* coords, const uint8_t* rgb8, int64_t n, const
     hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
     if (n > 0) hipLaunchKernelGGL(render_splat_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
     hipLaunchKernelGGL(render_resolve_kernel, dim3(blocks_for((npix + 3) / 4, 256)), dim3(256), 0, st, zbuf, rgb8, bg, npix, image);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+int64_t pcc_visibility_scratch_bytes(int32_t H, int32_t W) { return pcc_render_scratch_bytes(H, W); }
+
+int pcc_view_visibility(const int32_t* coords, int64_t n, const int32_t* right, const int32_t* up, const int32_t* front, int32_t u_min,
+                        int32_t v_max, int32_t ox, int32_t oy, int32_t scale, int32_t point_size, int32_t H, int32_t W, void* scratch,
+                        int64_t scratch_bytes, int32_t accumulate, int32_t* behind, int32_t* won, void* stream) {
+    if (int rc = check_view("pcc_view_visibility", right, up, front, scale, point_size, H, W, n)) return rc;
+    PCC_REQUIRE(n == 0 || (coords && behind && won), "pcc_view_visibility: null cloud or outputs with n > 0");
+    PCC_REQUIRE(scratch, "pcc_view_visibility: z-buffer required");
+    PCC_REQUIRE(scratch_bytes >= pcc_visibility_scratch_bytes(H, W), "pcc_view_visibility: scratch too small");
+    if (n == 0) return PCC_OK;                                // nothing to write, and the z-buffer is scratch: nothing to launch
+    const RenderView a = make_view(right, up, front, u_min, v_max, ox, oy, scale, point_size, H, W);
+    const int64_t npix = (int64_t)H * W;
+    hipStream_t st = as_stream(stream);
+    uint64_t* zbuf = reinterpret_cast<uint64_t*>(scratch);
+    hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
+    hipLaunchKernelGGL(render_splat_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
+    hipLaunchKernelGGL(visibility_gather_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf, accumulate != 0, behind, won);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
 }

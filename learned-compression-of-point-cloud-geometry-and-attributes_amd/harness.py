@@ -20,7 +20,7 @@ from . import render
 from .io import write_png
 from .metrics import PointCloudMetric
 from .normals import estimate_normals
-from .q_map import facing_score
+from .q_map import facing_score, visibility_score
 from .sparse import SparseTensor
 
 
@@ -169,13 +169,18 @@ def _extent(points, axis):
 
 
 def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path, view="front", H=1024, W=512, gradient=None, roi=None,
-                            save_images=False, details=None, facing=None):
+                            save_images=False, details=None, facing=None, visibility=None):
     """The three rows of evaluate_view_dep.py:139-301 for one frame -> {"uniform": row, "view": row, "roi": row}, each row
     {"bpp", "q_a", "q_g", "key", "psnr", "ssim"}.
 
     ``facing`` (a dict) appends a fourth row "facing", judged by the same rendered view: quality by the angle between each
     point's normal and the viewing ray (q_map.facing_score; evaluate_view_dep.py:354-376).  Its keys: ``radius`` of the normal
     estimation (3), ``camera`` (a position) or ``direction`` (the view's front axis when neither is given), ``floor`` (0.0).
+
+    ``visibility`` (a dict) appends a row "visible" after the others, judged by the same rendered view: quality by what the
+    views can show (render.visibility on the source's points at H x W, each view framing the source; q_map.visibility_score).
+    Its keys: ``views`` (a list of presets or (front, up) pairs; the judged view when left out), ``tolerance`` (2), ``falloff``
+    (8), ``floor`` (0.0), ``point_size`` (None: each frame's scale).  ``details["visibility"]`` receives (behind, score).
 
     ``view``: a preset of render.VIEWS or a (front, up) pair.  ``gradient=(axis, lo, hi)``: the view-dependent map, score =
     clip((p[axis] - lo) / (hi - lo), 0, 1) with axis 0..2 over x, y, z (:209-215; lo > hi makes quality rise towards
@@ -186,7 +191,7 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
 
     All four images (the source and the three reconstructions) are rendered in the SOURCE's frame.  ``save_images`` writes
     them as PNG under ``<base_path>/<experiment>/renders_view/`` (the reference's names, :188-278).  ``details`` (a dict)
-    receives ``{"source" | "uniform" | "view" | "roi" (| "facing"): (cloud, image)}`` for callers that want the tensors."""
+    receives ``{"source" | "uniform" | "view" | "roi" (| "facing") (| "visible"): (cloud, image)}`` for callers that want the tensors."""
     front, up = render._view(view)
     right, up, front = render.view_axes(front, up)
     tag = view if isinstance(view, str) else "custom"
@@ -212,6 +217,15 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
             direction = front
         normals, _ = estimate_normals(points, radius=facing.get("radius", 3))
         maps["facing"] = facing_score(points, normals, camera, direction, facing.get("floor", 0.0)).to(torch.float)
+    if visibility is not None:
+        unknown = set(visibility) - {"views", "tolerance", "falloff", "floor", "point_size"}
+        if unknown:
+            raise ValueError("visibility: unknown keys %s" % sorted(unknown))
+        behind, _ = render.visibility(points, visibility.get("views", [view]), H, W, point_size=visibility.get("point_size"), device=device)
+        vis_score = visibility_score(behind, visibility.get("tolerance", 2), visibility.get("falloff", 8), visibility.get("floor", 0.0))
+        maps["visible"] = vis_score.to(torch.float)
+        if details is not None:
+            details["visibility"] = (behind, vis_score)
     img_dir = os.path.join(base_path, experiment, "renders_view")
     if save_images:
         os.makedirs(img_dir, exist_ok=True)

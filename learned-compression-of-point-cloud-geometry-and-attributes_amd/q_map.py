@@ -7,7 +7,8 @@ reference's training-time generator, driven by Python's ``random`` like the refe
 seeded run draws the same maps — and returns it together with the lambda map used by the losses.
 ``uniform_map`` / ``gradient_map`` / ``view_dependent_map`` / ``roi_map`` build the fixed maps of the
 evaluation scripts (utils.py:436-445, evaluate_view_dep.py:207-260); ``facing_map`` is the second half of the view-dependent
-experiment (evaluate_view_dep.py:354-376): quality by the angle between a point's normal and the viewing ray.  Elementwise work
+experiment (evaluate_view_dep.py:354-376): quality by the angle between a point's normal and the viewing ray; ``visibility_map`` goes one step further and scores a point
+by what the judged views can show at all (render.visibility: how far it lies behind the z-buffer front).  Elementwise work
 on [N, 2] tensors; plain torch.
 """
 import math
@@ -66,6 +67,44 @@ def facing_map(coords_map, normals, q_g, q_a, camera=None, direction=None, floor
     """quality by how squarely a surface faces the viewer: score = floor + (1 - floor) * |n . v| (facing_score), channels
     [q_g * score, q_a * score]; ``normals``: float64 [N, 3] of normals.estimate_normals on the map's coordinates"""
     score = facing_score(coords_map.coords[:, 1:4], normals, camera, direction, floor)
+    return SparseTensor(torch.stack([float(q_g) * score, float(q_a) * score], dim=1).to(torch.float32).contiguous(), coordinate_map=coords_map)
+
+
+def visibility_score(behind, tolerance=2, falloff=8, floor=0.0):
+    """float64 [N]: floor + (1 - floor) * w from ``behind`` (integers: render.visibility's first result, voxels behind the
+    z-buffer front).  With hidden = max(behind - tolerance, 0): w = 1 where hidden == 0; w = max(0, 1 - hidden / falloff) where
+    hidden > 0 (0 when falloff == 0); w = 0 wherever behind == render.OFFSCREEN.  Float64 arithmetic on the integer input.
+
+    ``tolerance`` keeps the few voxels just under the visible surface (they shape what the decoder puts on the front),
+    ``falloff`` is the depth over which quality then runs out.  The defaults (2 and 8) are starting values read off a
+    prototype on the synthetic shell, NOT tuned against rate or quality."""
+    from .render import OFFSCREEN
+    tolerance, falloff, floor = float(tolerance), float(falloff), float(floor)
+    if not (tolerance >= 0 and falloff >= 0):
+        raise ValueError("visibility score: tolerance and falloff are non-negative (got %r, %r)" % (tolerance, falloff))
+    if not 0.0 <= floor <= 1.0:
+        raise ValueError("visibility score: floor is in [0, 1] (got %r)" % floor)
+    behind = torch.as_tensor(behind)
+    if behind.is_floating_point() or behind.is_complex() or behind.dtype == torch.bool or behind.dim() != 1:
+        raise ValueError("visibility score: behind is a one-dimensional integer tensor (render.visibility's first result)")
+    b = behind.to(torch.int64)
+    hidden = torch.clamp(b.to(torch.float64) - tolerance, min=0.0)
+    if falloff > 0:
+        w = torch.clamp(1.0 - hidden / falloff, min=0.0)
+    else:
+        w = (hidden == 0).to(torch.float64)
+    w = torch.where(b == OFFSCREEN, torch.zeros_like(w), w)
+    return floor + (1.0 - floor) * w
+
+
+def visibility_map(coords_map, behind, q_g, q_a, tolerance=2, falloff=8, floor=0.0):
+    """quality by what the judged views can show: score = visibility_score(behind, ...), channels [q_g * score, q_a * score]
+    (float64 products, cast to float32 — as facing_map).  ``behind`` must be in the row order of ``coords_map.coords``: compute
+    it on those rows, ``behind, _ = render.visibility(coords_map.coords[:, 1:4], views, H, W)``."""
+    score = visibility_score(behind, tolerance, falloff, floor)
+    if score.shape[0] != coords_map.n:
+        raise ValueError("visibility map: %d scores for %d coordinates" % (score.shape[0], coords_map.n))
+    score = score.to(coords_map.device)
     return SparseTensor(torch.stack([float(q_g) * score, float(q_a) * score], dim=1).to(torch.float32).contiguous(), coordinate_map=coords_map)
 
 

@@ -15,6 +15,9 @@ order before the call, so for a duplicate-free cloud the tie goes to the smaller
 What differs from open3d: no perspective (the reference narrows the field of view to its minimum, :340, which is close to
 orthographic), square integer splats instead of round anti-aliased GL points, an integer ``scale`` in place of ``zoom``.
 
+``visibility`` is the way back from such an image to the points (``pcc_view_visibility``): per point, how many voxels it lies
+behind the z-buffer front of the given views and how many pixels show it — what q_map.visibility_map builds its quality map from.
+
 ``view_metrics`` restates scikit-image's formulas in float64 (``pcc_image_compare``).  scikit-image is no dependency of
 this project and was not at hand: the ``yuv_from_rgb`` coefficients, the SSIM constants (K1 = 0.01, K2 = 0.03, 7 x 7
 uniform window, sample covariance, crop of 3) and the data-range rule of ``peak_signal_noise_ratio`` are recalled from its
@@ -33,6 +36,8 @@ VIEWS = {"front": ((0, 0, 1), (0, 1, 0)), "side": ((-1, 0, 0), (0, 1, 0))}
 VIEWS_MVUB = {"front": ((0, -1, 0), (0, 0, 1)), "side": ((-1, 0, 0), (0, 0, 1))}
 
 COORD_LIMIT = _lib.PCC.COORD_LIMIT
+OFFSCREEN = _lib.PCC.VIS_OFFSCREEN             # ``visibility``'s ``behind`` of a point no pixel of whose splat is inside the image
+MAX_DIM = 8192                                 # the largest image side the renderer takes (csrc/render.hip, RENDER_MAX_DIM)
 
 
 def _axis(v, name):
@@ -151,6 +156,84 @@ def render_view(cloud, front, up, H, W, frame=None, point_size=None, background=
                                 u_min, v_max, ox, oy, scale, point_size, int(H), int(W), ptr(bg), ptr(zbuf), zbytes, ptr(image),
                                 _lib.stream()))
     return image
+
+
+def _views(views):
+    """a non-empty list of preset names / (front, up) pairs -> [(right, up, front), ...]; ValueError otherwise"""
+    if isinstance(views, str) or not isinstance(views, (list, tuple)):
+        raise ValueError("views is a list of preset names of %s or (front, up) pairs, got %r" % (sorted(VIEWS), views))
+    if len(views) == 0:
+        raise ValueError("views is empty: visibility needs at least one view")
+    out = []
+    for view in views:
+        try:
+            front, up = _view(view)
+        except TypeError:
+            raise ValueError("a view is a preset name of %s or a (front, up) pair, got %r" % (sorted(VIEWS), view)) from None
+        out.append(view_axes(front, up))
+    return out
+
+
+def visibility(cloud, views, H, W, frames=None, point_size=None, device=None):
+    """Which points do the images of ``views`` show?  -> (behind, won): int32 [N] tensors on the GPU in the INPUT's row order
+    (csrc/render.hip, ``pcc_view_visibility``).
+
+    For one view, with the geometry, clipping and winner rule of ``render_view`` at H x W: ``behind[i]`` is the minimum, over
+    the pixels of point i's splat that lie inside the image, of (the largest d splatted onto the pixel) - d_i: 0 exactly when
+    the point is on the z-buffer front in at least one pixel, otherwise how many voxels deep it lies behind what the view
+    shows; ``OFFSCREEN`` when no pixel of its splat is inside the image.  ``won[i]`` is the number of pixels that show point i
+    (rows are put in canonical (x, y, z) order before the call, as in ``render_view``, so ties between equal depths go to the
+    smaller (x, y, z) whatever the input order; ``behind`` does not depend on ties).  Over several views ``behind`` is the
+    minimum and ``won`` the sum.  All integer and bitwise reproducible.
+
+    ``cloud``: [N, >= 3] with integer coordinates (colours are not needed).  ``views``: a non-empty list of preset names of
+    ``VIEWS`` or (front, up) pairs.  ``frames``: None (every view frames the cloud itself at H x W) or one ``view_frame`` result
+    per view (a reconstruction is analysed in its source's frames).  ``point_size=None`` means each frame's scale.  Not a
+    camera: orthographic, axis views only, square splats."""
+    cloud, xyz = _int_xyz(cloud)
+    axes = _views(views)
+    if frames is not None:
+        if not isinstance(frames, (list, tuple)) or len(frames) != len(axes):
+            raise ValueError("frames is None or one view_frame result per view (%d views)" % len(axes))
+        if any(not isinstance(fr, (list, tuple)) or len(fr) != 7 for fr in frames):
+            raise ValueError("a frame is a view_frame result: (u_min, u_max, v_min, v_max, scale, ox, oy)")
+    H, W = int(H), int(W)
+    if not (1 <= H <= MAX_DIM and 1 <= W <= MAX_DIM):
+        raise ValueError("H and W must be 1 .. %d (got %d x %d)" % (MAX_DIM, H, W))
+    dev = torch.device(device) if device is not None else (cloud.device if cloud.is_cuda else torch.device("cuda:0"))
+    if dev.type != "cuda":
+        raise ValueError("visibility runs on the GPU: got device %s" % dev)
+    n = int(cloud.shape[0])
+    if n and int(xyz.abs().max()) > COORD_LIMIT:
+        raise ValueError("visibility: coordinates beyond +-%d" % COORD_LIMIT)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        xyz = xyz.to(dev)
+        coords = torch.cat([torch.zeros((n, 1), dtype=torch.int32, device=dev), xyz], dim=1).contiguous()
+        perm = None
+        if n > 1:                                      # canonical (x, y, z) order: the tie rule's "lowest row"
+            nbytes = L.pcc_sort_scratch_bytes(n)
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            perm = torch.empty(n, dtype=torch.int32, device=dev)
+            check(L.pcc_sort_coords(ptr(coords), n, ptr(perm), ptr(scratch), nbytes, _lib.stream()))
+            perm = perm.long()
+            coords = coords[perm].contiguous()
+        zbytes = L.pcc_visibility_scratch_bytes(H, W)
+        zbuf = torch.empty(max(zbytes, 8), dtype=torch.uint8, device=dev)
+        behind = torch.empty(n, dtype=torch.int32, device=dev)
+        won = torch.empty(n, dtype=torch.int32, device=dev)
+        if n == 0:                                     # nothing to frame and nothing to ask
+            return behind, won
+        for k, (r, u, f) in enumerate(axes):
+            frame = view_frame(xyz, f, u, H, W) if frames is None else frames[k]
+            u_min, _, _, v_max, scale, ox, oy = (int(v) for v in frame)
+            size = scale if point_size is None else int(point_size)
+            vecs = [np.asarray(a, dtype=np.int32) for a in (r, u, f)]
+            check(L.pcc_view_visibility(ptr(coords), n, ptr(vecs[0]), ptr(vecs[1]), ptr(vecs[2]), u_min, v_max, ox, oy, scale, size, H, W,
+                                        ptr(zbuf), zbytes, int(k > 0), ptr(behind), ptr(won), _lib.stream()))
+        if perm is not None:                           # back to the input's row order
+            behind, won = torch.empty_like(behind).index_copy_(0, perm, behind), torch.empty_like(won).index_copy_(0, perm, won)
+    return behind, won
 
 
 def data_range_of(ref_min):

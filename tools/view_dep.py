@@ -11,7 +11,10 @@ numbers the reference keeps per sequence (:58-77) are arguments here; left out, 
 usage: view_dep.py [config1 | config2 | frame.ply] [--out DIR] [--view front|side] [--height 1024] [--width 512]
                    [--q-g 0.4] [--q-a 0.8] [--gradient AXIS LO HI] [--roi AXIS PLANE] [--weights W.pt] [--repeat N]
                    [--facing [--facing-radius 3] [--facing-floor 0.0]]     (a fourth row: quality by the angle between the
-                   points' normals and the viewing direction)"""
+                   points' normals and the viewing direction)
+                   [--visibility [--vis-views front side] [--vis-tolerance 2] [--vis-falloff 8] [--vis-floor 0.0]]     (a row
+                   "visible": quality by how far a point lies behind what the views show, render.visibility; --vis-views are names
+                   of the active view table, the judged view when left out)"""
 import argparse
 import csv
 import json
@@ -46,6 +49,11 @@ def main():
     ap.add_argument("--facing", action="store_true", help="add the facing row: quality by the normals' angle to the view's front axis")
     ap.add_argument("--facing-radius", type=int, default=3)
     ap.add_argument("--facing-floor", type=float, default=0.0)
+    ap.add_argument("--visibility", action="store_true", help="add the visible row: quality by the depth behind the z-buffer front of the views")
+    ap.add_argument("--vis-views", nargs="+", choices=sorted(render.VIEWS), help="views whose visibility counts (default: the judged view)")
+    ap.add_argument("--vis-tolerance", type=int, default=2)
+    ap.add_argument("--vis-falloff", type=int, default=8)
+    ap.add_argument("--vis-floor", type=float, default=0.0)
     ap.add_argument("--repeat", type=int, default=0, help="time render_view and view_metrics over N further calls")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
@@ -67,9 +75,15 @@ def main():
     roi = None if a.roi is None else (int(a.roi[0]), a.roi[1])
     details = {}
     facing = {"radius": a.facing_radius, "floor": a.facing_floor} if a.facing else None
+    visibility = None
+    if a.visibility:
+        table = render.VIEWS_MVUB if a.mvub else render.VIEWS
+        visibility = {"views": [table[name] for name in (a.vis_views or [a.view])], "tolerance": a.vis_tolerance, "falloff": a.vis_falloff,
+                      "floor": a.vis_floor}
     t0 = time.time()
     rows = evaluate_view_dependent(a.experiment, model, data, a.q_a, a.q_g, dev, a.out, view=view if a.mvub else a.view, H=a.height,
-                                   W=a.width, gradient=gradient, roi=roi, save_images=True, details=details, facing=facing)
+                                   W=a.width, gradient=gradient, roi=roi, save_images=True, details=details, facing=facing,
+                                   visibility=visibility)
     t_all = time.time() - t0
     path = os.path.join(a.out, a.experiment, "view_dep.csv")
     with open(path, "w", newline="") as f:
@@ -80,8 +94,13 @@ def main():
     for key, row in rows.items():
         print("%-8s bpp %.4f  view psnr %.3f dB  view ssim %.5f" % (key, row["bpp"], row["psnr"], row["ssim"]))
     result = {"frame": a.frame, "n_points": int(pts.shape[0]), "H": a.height, "W": a.width, "view": a.view, "t_three_rows_s": t_all}
-    if a.facing:
-        result["t_four_rows_s"] = result.pop("t_three_rows_s")
+    if a.facing or a.visibility:
+        result["t_%s_rows_s" % {4: "four", 5: "five"}[len(rows)]] = result.pop("t_three_rows_s")
+    if a.visibility:
+        behind = details["visibility"][0]
+        result["visibility"] = {"views": a.vis_views or [a.view], "tolerance": a.vis_tolerance, "falloff": a.vis_falloff, "floor": a.vis_floor,
+                                "on_front": int((behind == 0).sum()), "within_tolerance": int((behind <= a.vis_tolerance).sum()),
+                                "offscreen": int((behind == render.OFFSCREEN).sum())}
     if a.repeat > 0:
         src, ref_img = details["source"]
         rec, img = details["uniform"]
