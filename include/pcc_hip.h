@@ -614,6 +614,42 @@ int pcc_pcqm_features(const int32_t* coords_r, int64_t n_r, const uint64_t* keys
  * conditions: bad axes, scale outside 1..64, point_size outside 1..16, H or W outside 1..8192, n above
  * 2^32 - 2, a null cloud or null outputs with n > 0, a null or short z-buffer.  n == 0 is valid, launches
  * nothing and touches no array.  Not a camera: orthographic, axis views only, square splats.
+ *
+ * pcc_render_camera and pcc_camera_visibility are those two operators for a PINHOLE CAMERA at a position.  The
+ * camera crosses this interface as integers only (HOST arrays and scalars), and no kernel uses floating point:
+ *   pos_q   int32[3]    rint(16 position): 1/16 voxel, |pos_q| <= 2^24 (2^20 voxels)
+ *   axes_q  int32[3][3] rint(2^14 [right; up; front]), row-major, every entry in [-2^14, 2^14]; front points from
+ *                       the scene to the camera (open3d's set_front), right = up x front
+ *   focal_q int32       rint(16 focal), focal in pixels: 1 .. 2^20
+ *   near_q  int32       rint(16 near), 1/16 voxel: >= 1
+ *   H, W    int32       1 .. 8192
+ *   ps_q    int32       rint(16 point_size), the voxel's edge in 1/16 voxel: 1 .. 256
+ * For a row p (|coordinate| <= PCC_COORD_LIMIT, else it draws nothing), in int64:
+ *   e = 16 p - pos_q;  U = right_q . e;  V = up_q . e;  D = -(front_q . e)         (D: depth, 2^-18 voxel)
+ *   drawn <=> D >= near_q 2^14 (a point behind the camera is not drawn)
+ *   X = floor(focal_q U / D);  Y = floor(focal_q V / D)                (1/16 pixel from the principal point (W/2, H/2))
+ *   s = clamp(ceil(focal_q ps_q 2^10 / D), 1, 16)                                (the projected voxel edge, pixels)
+ *   col0 = floor((8 W + X - 8 s) / 16);  row0 = floor((8 H - Y - 8 s) / 16)
+ *   the splat covers columns col0 .. col0 + s - 1 and rows row0 .. row0 + s - 1; pixels outside the image are
+ *   dropped one by one;  dk = D >> 10 (depth key, 1/256 voxel, 16 <= dk < 2^30)
+ * Division rounds as written (floor towards -inf, ceil towards +inf).  |focal_q U| < 2^60 under the limits above
+ * (|U| <= 3 2^14 (2^24 + 16 PCC_COORD_LIMIT) < 2^40); the entries recompute the bound from their arguments and refuse
+ * a camera that would break it.  A pixel shows the drawn point with the smallest dk and, among equal dk, the lowest
+ * row index: a 64-bit atomic maximum of ((0x7FFFFFFF - dk) << 32) | (0xFFFFFFFF - row) on pcc_render_view's z-buffer
+ * (pcc_render_scratch_bytes(H, W) bytes), cleared and resolved by pcc_render_view's kernels.  At most s^2 <= 256
+ * atomics per point.  Bitwise reproducible.
+ * pcc_render_camera: coords [n,4] (batch ignored), rgb8 uint8 [n,3], background HOST 3 bytes, image uint8 [H,W,3];
+ * n == 0 is valid (every pixel is background).
+ * pcc_camera_visibility, for every row i (one thread walks its splat again; no atomics beyond the splat's):
+ *   behind[i] = the minimum over the row's pixels inside the image of (dk_i - dk_front(pixel)) >> 8: whole voxels
+ *               behind the z-buffer front; 0 = within one voxel of it.  Always >= 0.
+ *   won[i]    = the number of pixels whose word is the row's own; won[i] > 0 implies behind[i] == 0.
+ *   depth[i]  = dk_i.
+ *   A row that is not drawn, or whose splat lies wholly outside the image: behind = depth = PCC_VIS_OFFSCREEN, won = 0.
+ * accumulate != 0 folds into what the arrays hold: min / sum / min.  n == 0 launches nothing and touches no array.
+ * Both refuse before any launch (PCC_ERR_ARG): a null pointer (cloud or outputs with n > 0, camera arrays,
+ * background, z-buffer, image), a short z-buffer, any value outside the table above, n above 2^32 - 2.  Not a lens
+ * model: no distortion, square splats, no anti-aliasing, and holes open once a voxel projects beyond 16 pixels.
  * ------------------------------------------------------------------------------------- */
 #define PCC_VIS_OFFSCREEN 2147483647
 int64_t pcc_render_scratch_bytes(int32_t H, int32_t W);
@@ -626,6 +662,14 @@ int pcc_view_visibility(const int32_t* coords, int64_t n, const int32_t* right, 
                         const int32_t* front, int32_t u_min, int32_t v_max, int32_t ox, int32_t oy, int32_t scale,
                         int32_t point_size, int32_t H, int32_t W, void* scratch, int64_t scratch_bytes,
                         int32_t accumulate, int32_t* behind, int32_t* won, void* stream);
+int pcc_render_camera(const int32_t* coords, const uint8_t* rgb8, int64_t n, const int32_t* pos_q,
+                      const int32_t* axes_q, int32_t focal_q, int32_t near_q, int32_t H, int32_t W, int32_t ps_q,
+                      const uint8_t* background, void* scratch, int64_t scratch_bytes, uint8_t* image,
+                      void* stream);
+int pcc_camera_visibility(const int32_t* coords, int64_t n, const int32_t* pos_q, const int32_t* axes_q,
+                          int32_t focal_q, int32_t near_q, int32_t H, int32_t W, int32_t ps_q, void* scratch,
+                          int64_t scratch_bytes, int32_t accumulate, int32_t* behind, int32_t* won,
+                          int32_t* depth, void* stream);
 int32_t pcc_image_compare_tile(void);
 int64_t pcc_image_compare_scratch_bytes(int32_t H, int32_t W);
 int pcc_image_compare(const uint8_t* ref, const uint8_t* img, int32_t H, int32_t W, void* scratch,

@@ -35,6 +35,9 @@ NO_SCRATCH = {
     # the perceptual metric (csrc/pcqm.hip): 20 running sums per point live through up to 4,218 probes and gathers; a spilled
     # one would put a scratch round trip behind every neighbour.  The kappa kernel shares the normals' Jacobi over named scalars
     "pcqm": ("surface_variation_kernel", "pcqm_features_kernel"),
+    # the camera views (csrc/render.hip): three emulated 64-bit divisions per point sit in front of up to 256 atomics or reads;
+    # a spill among their operands would be a scratch round trip per point in two kernels that otherwise touch only the z-buffer
+    "render": ("camera_splat_kernel", "camera_gather_kernel"),
 }
 
 

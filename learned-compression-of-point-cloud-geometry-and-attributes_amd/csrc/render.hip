@@ -20,6 +20,10 @@
 // its splat again and reads how far the point lies behind the z-buffer front (`behind`, the minimum over its pixels) and how
 // many pixels it owns (`won`).  No image is resolved.
 //
+// pcc_render_camera and pcc_camera_visibility are the same two operators for a pinhole camera at a position: a perspective
+// projection in int64 (camera_project below) between the shared clear and resolve kernels, and a walk back that also
+// returns each point's depth.
+//
 // pcc_image_compare replaces rgb2yuv +peak_signal_noise_ratio + structural_similarity (evaluate_view_dep.py:196-204) by
 // their raw sums in float64: one workgroup per IC_TILE x IC_TILE tile converts the tile and its 6-pixel apron to YUV one
 // channel at a time into LDS, adds the squared differences of the pixels it owns and the SSIM map values of the 7 x 7
@@ -133,8 +137,110 @@ __global__ __launch_bounds__(256) void visibility_gather_kernel(const int32_t* _
     won[row] = count;
 }
 
+// ---- pinhole camera: perspective splat and walk back, all int64 ----
+// The camera crosses the ABI as integers only (pcc_hip.h): pos in 1/16 voxel, the three axes in 2^-14, focal in 1/16 pixel,
+// near in 1/16 voxel, the voxel edge ps in 1/16 voxel.  For a row p:
+//   e = 16 p - pos;  U = right . e, V = up . e, D = -(front . e)   (2^-18 voxel; front points from the scene to the camera)
+//   drawn <=> D >= near 2^14;  X = floor(focal U / D), Y = floor(focal V / D)   (1/16 pixel from the principal point)
+//   s = clamp(ceil(focal ps 2^10 / D), 1, 16);  col0 = floor((8 W + X - 8 s) / 16), row0 = floor((8 H - Y - 8 s) / 16)
+//   depth key dk = D >> 10 (1/256 voxel); the z-buffer word is ((0x7FFFFFFF - dk) << 32) | (0xFFFFFFFF - row)
+// Bounds, which the host entry re-derives from the arguments it is given (camera_check): |e_k| <= |pos_k| + 16 COORD_LIMIT <
+// 2^24 + 2^21, an axis row has entries of at most 2^14, so |U|, |V|, |D| < 3 2^14 (2^24 + 2^21) < 2^40, |focal U| < 2^60, dk <
+// 2^30 and dk >= 16 near >= 16: the high half of a drawn pixel's word is in (2^30, 2^31) and never 0.  The clear and resolve
+// kernels above are shared with the orthographic view: the word layout is theirs, the larger word is the nearer point and,
+// among equal dk, the lower row.
+struct CameraView {
+    int32_t pos[3], ax[3][3];
+    int32_t focal, near, ps, H, W;
+};
+
+struct CameraSplat {                 // the splat of one point clipped to the image: rows r0 .. r1 - 1, columns c0 .. c1 - 1
+    int32_t r0, r1, c0, c1;
+    uint32_t dk;
+};
+
+// floor(a / b) for b > 0, through one unsigned division (C++'s `/` truncates towards zero)
+__device__ __forceinline__ int64_t camera_floordiv(int64_t a, uint64_t b) {
+    return a >= 0 ? (int64_t)((uint64_t)a / b) : -(int64_t)(((uint64_t)(-a) + b - 1) / b);
+}
+
+// false when the row draws nothing: a coordinate out of range, or in front of the near plane (behind the camera included)
+__device__ __forceinline__ bool camera_project(const int4 c, const CameraView& a, CameraSplat& out) {
+    if (!coord_in_range(0, c.y, c.z, c.w)) return false;
+    const int64_t e0 = 16 * (int64_t)c.y - a.pos[0], e1 = 16 * (int64_t)c.z - a.pos[1], e2 = 16 * (int64_t)c.w - a.pos[2];
+    const int64_t U = a.ax[0][0] * e0 + a.ax[0][1] * e1 + a.ax[0][2] * e2;
+    const int64_t V = a.ax[1][0] * e0 + a.ax[1][1] * e1 + a.ax[1][2] * e2;
+    const int64_t D = -(a.ax[2][0] * e0 + a.ax[2][1] * e1 + a.ax[2][2] * e2);
+    if (D < ((int64_t)a.near << 14)) return false;
+    const uint64_t d = (uint64_t)D;
+    const int64_t X = camera_floordiv((int64_t)a.focal * U, d), Y = camera_floordiv((int64_t)a.focal * V, d);
+    const uint64_t edge = ((((uint64_t)a.focal * (uint64_t)a.ps) << 10) + d - 1) / d;
+    const int64_t s = edge < 1 ? 1 : (edge > 16 ? 16 : (int64_t)edge);
+    const int64_t col0 = (8 * (int64_t)a.W + X - 8 * s) >> 4, row0 = (8 * (int64_t)a.H - Y - 8 * s) >> 4;   // >> floors
+    const int64_t c0 = col0 < 0 ? 0 : col0, c1 = col0 + s > a.W ? a.W : col0 + s;
+    const int64_t r0 = row0 < 0 ? 0 : row0, r1 = row0 + s > a.H ? a.H : row0 + s;
+    out.dk = (uint32_t)(d >> 10);
+    // an empty range is stored as 0 .. 0: the clipped bounds of a splat far outside the image do not fit 32 bits
+    const bool inside = c0 < c1 && r0 < r1;
+    out.c0 = inside ? (int32_t)c0 : 0; out.c1 = inside ? (int32_t)c1 : 0;
+    out.r0 = inside ? (int32_t)r0 : 0; out.r1 = inside ? (int32_t)r1 : 0;
+    return true;
+}
+
+__device__ __forceinline__ uint64_t camera_word(uint32_t dk, int64_t row) {
+    return ((uint64_t)(0x7FFFFFFFu - dk) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)row);
+}
+
+// one thread per point, at most 16 x 16 atomics each
+__global__ __launch_bounds__(256) void camera_splat_kernel(const int32_t* __restrict__ coords, int64_t n, CameraView a,
+                                                           uint64_t* __restrict__ zbuf) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    const int4 c = reinterpret_cast<const int4*>(coords)[row];                  // (batch, x, y, z): the batch is ignored
+    CameraSplat sp;
+    if (!camera_project(c, a, sp)) return;
+    const uint64_t word = camera_word(sp.dk, row);
+    for (int32_t py = sp.r0; py < sp.r1; ++py)
+        for (int32_t px = sp.c0; px < sp.c1; ++px)
+            atomicMax(reinterpret_cast<unsigned long long*>(zbuf) + ((int64_t)py * a.W + px), (unsigned long long)word);
+}
+
+// the way back, as visibility_gather_kernel: behind in whole voxels (dk differences >> 8), won, and the point's own depth key
+__global__ __launch_bounds__(256) void camera_gather_kernel(const int32_t* __restrict__ coords, int64_t n, CameraView a,
+                                                            const uint64_t* __restrict__ zbuf, int accumulate,
+                                                            int32_t* __restrict__ behind, int32_t* __restrict__ won,
+                                                            int32_t* __restrict__ depth) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    const int4 c = reinterpret_cast<const int4*>(coords)[row];
+    int32_t best = PCC_VIS_OFFSCREEN, count = 0, dist = PCC_VIS_OFFSCREEN;
+    CameraSplat sp;
+    if (camera_project(c, a, sp) && sp.r0 < sp.r1) {
+        const uint64_t own = camera_word(sp.dk, row);
+        dist = (int32_t)sp.dk;
+        for (int32_t py = sp.r0; py < sp.r1; ++py) {
+            for (int32_t px = sp.c0; px < sp.c1; ++px) {
+                const uint64_t word = zbuf[(int64_t)py * a.W + px];
+                const uint32_t dk_front = 0x7FFFFFFFu - (uint32_t)(word >> 32);     // <= dk: this row took part in the maximum
+                const int32_t gap = (int32_t)((sp.dk - dk_front) >> 8);
+                best = gap < best ? gap : best;
+                count += word == own;
+            }
+        }
+    }
+    if (accumulate) {
+        const int32_t old_b = behind[row], old_d = depth[row];
+        best = old_b < best ? old_b : best;
+        dist = old_d < dist ? old_d : dist;
+        count += won[row];
+    }
+    behind[row] = best;
+    won[row] = count;
+    depth[row] = dist;
+}
+
 // ---- image metrics ----
-constexpr int IC_TILE = 32;                  // pixels a workgroup owns per side
+constexpr int IC_TILE = 32;                 // pixels a workgroup owns per side
 constexpr int IC_WIN = 7;                     // structural_similarity's window
 constexpr int IC_SPAN = IC_TILE + IC_WIN - 1; // the tile and its apron
 constexpr int IC_THREADS = 256;
@@ -264,6 +370,47 @@ static RenderView make_view(const int32_t* right, const int32_t* up, const int32
     return a;
 }
 
+constexpr int32_t CAMERA_POS_MAX = 1 << 24;      // 2^20 voxels in 1/16 voxel
+constexpr int32_t CAMERA_AXIS_ONE = 1 << 14;
+constexpr int32_t CAMERA_FOCAL_MAX = 1 << 20;
+
+// the checks pcc_render_camera and pcc_camera_visibility share: the table of pcc_hip.h, then the overflow bound of the
+// projection worked out from THESE arguments rather than taken from the table
+static int check_camera(const char* who, const int32_t* pos_q, const int32_t* axes_q, int32_t focal_q, int32_t near_q, int32_t ps_q,
+                        int32_t H, int32_t W, int64_t n) {
+    PCC_REQUIRE(pos_q && axes_q, "%s: camera position and axes required", who);
+    for (int k = 0; k < 3; ++k)
+        PCC_REQUIRE(pos_q[k] >= -CAMERA_POS_MAX && pos_q[k] <= CAMERA_POS_MAX, "%s: pos_q[%d] = %d is beyond +-2^24 (2^20 voxels)", who, k,
+                    pos_q[k]);
+    for (int k = 0; k < 9; ++k)
+        PCC_REQUIRE(axes_q[k] >= -CAMERA_AXIS_ONE && axes_q[k] <= CAMERA_AXIS_ONE, "%s: axes_q[%d] = %d is beyond +-2^14", who, k, axes_q[k]);
+    PCC_REQUIRE(focal_q >= 1 && focal_q <= CAMERA_FOCAL_MAX, "%s: focal_q must be 1 .. 2^20 (got %d)", who, focal_q);
+    PCC_REQUIRE(near_q >= 1, "%s: near_q must be at least 1 (got %d)", who, near_q);
+    PCC_REQUIRE(ps_q >= 1 && ps_q <= 256, "%s: ps_q must be 1 .. 256 (got %d)", who, ps_q);
+    PCC_REQUIRE(H >= 1 && H <= RENDER_MAX_DIM && W >= 1 && W <= RENDER_MAX_DIM, "%s: H and W must be 1 .. %d (got %d x %d)", who,
+                RENDER_MAX_DIM, H, W);
+    PCC_REQUIRE(n >= 0 && n <= 0xFFFFFFFEll, "%s: 0 .. 2^32 - 2 points", who);
+    for (int r = 0; r < 3; ++r) {                         // |axis . e| <= sum |axis_k| (|pos_k| + 16 COORD_LIMIT), < 2^41 whatever the caller gave
+        int64_t reach = 0;
+        for (int k = 0; k < 3; ++k) {
+            const int64_t ax = axes_q[3 * r + k], p = pos_q[k];
+            reach += (ax < 0 ? -ax : ax) * ((p < 0 ? -p : p) + 16 * (int64_t)COORD_LIMIT);
+        }
+        PCC_REQUIRE(reach < (1ll << 40) && reach * focal_q < (1ll << 60) && (reach >> 10) < 0x7FFFFFFFll,
+                    "%s: the projection of axis %d would leave its 60 bits", who, r);
+    }
+    return PCC_OK;
+}
+
+static CameraView make_camera(const int32_t* pos_q, const int32_t* axes_q, int32_t focal_q, int32_t near_q, int32_t ps_q, int32_t H,
+                              int32_t W) {
+    CameraView a;
+    for (int k = 0; k < 3; ++k) a.pos[k] = pos_q[k];
+    for (int k = 0; k < 9; ++k) a.ax[k / 3][k % 3] = axes_q[k];
+    a.focal = focal_q; a.near = near_q; a.ps = ps_q; a.H = H; a.W = W;
+    return a;
+}
+
 }  // namespace pcc
 
 using namespace pcc;
@@ -312,6 +459,46 @@ int pcc_view_visibility(const int32_t* coords, int64_t n, const int32_t* right, 
     hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
     hipLaunchKernelGGL(render_splat_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
     hipLaunchKernelGGL(visibility_gather_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf, accumulate != 0, behind, won);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+int pcc_render_camera(const int32_t* coords, const uint8_t* rgb8, int64_t n, const int32_t* pos_q, const int32_t* axes_q, int32_t focal_q,
+                      int32_t near_q, int32_t H, int32_t W, int32_t ps_q, const uint8_t* background, void* scratch, int64_t scratch_bytes,
+                      uint8_t* image, void* stream) {
+    if (int rc = check_camera("pcc_render_camera", pos_q, axes_q, focal_q, near_q, ps_q, H, W, n)) return rc;
+    PCC_REQUIRE(background, "pcc_render_camera: background required");
+    PCC_REQUIRE(n == 0 || (coords && rgb8), "pcc_render_camera: null cloud with n > 0");
+    PCC_REQUIRE(scratch && image, "pcc_render_camera: z-buffer and image required");
+    PCC_REQUIRE(scratch_bytes >= pcc_render_scratch_bytes(H, W), "pcc_render_camera: scratch too small");
+    const CameraView a = make_camera(pos_q, axes_q, focal_q, near_q, ps_q, H, W);
+    const int64_t npix = (int64_t)H * W;
+    const uint32_t bg = (uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16);
+    hipStream_t st = as_stream(stream);
+    uint64_t* zbuf = reinterpret_cast<uint64_t*>(scratch);
+    hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
+    if (n > 0) hipLaunchKernelGGL(camera_splat_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
+    hipLaunchKernelGGL(render_resolve_kernel, dim3(blocks_for((npix + 3) / 4, 256)), dim3(256), 0, st, zbuf, rgb8, bg, npix, image);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+int pcc_camera_visibility(const int32_t* coords, int64_t n, const int32_t* pos_q, const int32_t* axes_q, int32_t focal_q, int32_t near_q,
+                          int32_t H, int32_t W, int32_t ps_q, void* scratch, int64_t scratch_bytes, int32_t accumulate, int32_t* behind,
+                          int32_t* won, int32_t* depth, void* stream) {
+    if (int rc = check_camera("pcc_camera_visibility", pos_q, axes_q, focal_q, near_q, ps_q, H, W, n)) return rc;
+    PCC_REQUIRE(n == 0 || (coords && behind && won && depth), "pcc_camera_visibility: null cloud or outputs with n > 0");
+    PCC_REQUIRE(scratch, "pcc_camera_visibility: z-buffer required");
+    PCC_REQUIRE(scratch_bytes >= pcc_render_scratch_bytes(H, W), "pcc_camera_visibility: scratch too small");
+    if (n == 0) return PCC_OK;                                // nothing to write, and the z-buffer is scratch: nothing to launch
+    const CameraView a = make_camera(pos_q, axes_q, focal_q, near_q, ps_q, H, W);
+    const int64_t npix = (int64_t)H * W;
+    hipStream_t st = as_stream(stream);
+    uint64_t* zbuf = reinterpret_cast<uint64_t*>(scratch);
+    hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
+    hipLaunchKernelGGL(camera_splat_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
+    hipLaunchKernelGGL(camera_gather_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf, accumulate != 0, behind, won,
+                       depth);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
 }

@@ -169,7 +169,7 @@ def _extent(points, axis):
 
 
 def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path, view="front", H=1024, W=512, gradient=None, roi=None,
-                            save_images=False, details=None, facing=None, visibility=None):
+                            save_images=False, details=None, facing=None, visibility=None, camera=None):
     """The three rows of evaluate_view_dep.py:139-301 for one frame -> {"uniform": row, "view": row, "roi": row}, each row
     {"bpp", "q_a", "q_g", "key", "psnr", "ssim"}.
 
@@ -191,17 +191,35 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
 
     All four images (the source and the three reconstructions) are rendered in the SOURCE's frame.  ``save_images`` writes
     them as PNG under ``<base_path>/<experiment>/renders_view/`` (the reference's names, :188-278).  ``details`` (a dict)
-    receives ``{"source" | "uniform" | "view" | "roi" (| "facing") (| "visible"): (cloud, image)}`` for callers that want the tensors."""
-    front, up = render._view(view)
-    right, up, front = render.view_axes(front, up)
-    tag = view if isinstance(view, str) else "custom"
+    receives ``{"source" | "uniform" | "view" | "roi" (| "facing") (| "visible"): (cloud, image)}`` for callers that want the tensors.
+
+    ``camera`` (a render.Camera): the viewer stands at a point.  The source and every reconstruction are then rendered and
+    judged by render.render_camera, and ``view``, ``H`` and ``W`` are not used (the image size is the camera's; the images are
+    tagged "camera").  The default gradient runs along the camera's dominant front axis and the default region of interest
+    along its dominant right axis; ``facing`` defaults its ``camera`` to the camera's position; ``visibility`` takes ``cameras``
+    (a list of render.Camera; ``[camera]`` when left out) in place of ``views`` and uses render.camera_visibility, with
+    ``point_size`` a voxel edge (1.0).  With ``camera=None`` nothing changes."""
+    if camera is not None:
+        if not isinstance(camera, render.Camera):
+            raise ValueError("camera is a render.Camera, got %r" % (camera,))
+        right, up, front = ([float(v) for v in a] for a in (camera.right, camera.up, camera.front))
+        tag = "camera"
+    else:
+        front, up = render._view(view)
+        right, up, front = render.view_axes(front, up)
+        tag = view if isinstance(view, str) else "custom"
+
+    def dominant(axis):
+        mags = [abs(a) for a in axis]
+        return mags.index(max(mags))
+
     points = data["src"]["points"][0].to(device, dtype=torch.float)
     if gradient is None:
-        axis = [abs(a) for a in front].index(1)
+        axis = dominant(front)
         lo, hi = _extent(points, axis)
         gradient = (axis, lo, hi) if front[axis] > 0 else (axis, hi, lo)
     if roi is None:
-        axis = [abs(a) for a in right].index(1)
+        axis = dominant(right)
         lo, hi = _extent(points, axis)
         roi = (axis, (lo + hi) / 2.0)
     g_axis, g_lo, g_hi = gradient
@@ -212,16 +230,24 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
         "roi": (points[:, r_axis] >= float(r_plane)).to(torch.float),
     }
     if facing is not None:
-        camera, direction = facing.get("camera"), facing.get("direction")
-        if camera is None and direction is None:
-            direction = front
+        eye, direction = facing.get("camera"), facing.get("direction")
+        if eye is None and direction is None:
+            if camera is not None:
+                eye = [float(v) for v in camera.position]
+            else:
+                direction = front
         normals, _ = estimate_normals(points, radius=facing.get("radius", 3))
-        maps["facing"] = facing_score(points, normals, camera, direction, facing.get("floor", 0.0)).to(torch.float)
+        maps["facing"] = facing_score(points, normals, eye, direction, facing.get("floor", 0.0)).to(torch.float)
     if visibility is not None:
-        unknown = set(visibility) - {"views", "tolerance", "falloff", "floor", "point_size"}
+        unknown = set(visibility) - {"views" if camera is None else "cameras", "tolerance", "falloff", "floor", "point_size"}
         if unknown:
             raise ValueError("visibility: unknown keys %s" % sorted(unknown))
-        behind, _ = render.visibility(points, visibility.get("views", [view]), H, W, point_size=visibility.get("point_size"), device=device)
+        if camera is None:
+            behind, _ = render.visibility(points, visibility.get("views", [view]), H, W, point_size=visibility.get("point_size"), device=device)
+        else:
+            size = visibility.get("point_size")
+            behind, _, _ = render.camera_visibility(points, visibility.get("cameras", [camera]), point_size=1.0 if size is None else size,
+                                                    device=device)
         vis_score = visibility_score(behind, visibility.get("tolerance", 2), visibility.get("falloff", 8), visibility.get("floor", 0.0))
         maps["visible"] = vis_score.to(torch.float)
         if details is not None:
@@ -234,14 +260,19 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
         qa = q_a if score is None else (float(q_a) * score).reshape(-1, 1)
         qg = q_g if score is None else (float(q_g) * score).reshape(-1, 1)
         src, rec, bpp, _, _ = compress_model_ours(experiment, model, data, qa, qg, device, base_path)
+        if camera is not None:
+            draw = lambda cloud: render.render_camera(cloud, camera)
+        else:
+            if frame is None:
+                frame = render.view_frame(src, front, up, H, W)
+            draw = lambda cloud: render.render_view(cloud, front, up, H, W, frame=frame)
         if ref_img is None:
-            frame = render.view_frame(src, front, up, H, W)
-            ref_img = render.render_view(src, front, up, H, W, frame=frame)
+            ref_img = draw(src)
             if save_images:
                 write_png(os.path.join(img_dir, "ref_%s.png" % tag), ref_img)
             if details is not None:
                 details["source"] = (src, ref_img)
-        img = render.render_view(rec, front, up, H, W, frame=frame)
+        img = draw(rec)
         m = render.view_metrics(ref_img, img)
         rows[key] = {"bpp": bpp, "q_a": q_a, "q_g": q_g, "key": key, "psnr": m["psnr"], "ssim": m["ssim"]}
         if save_images:

@@ -8,7 +8,8 @@ seeded run draws the same maps — and returns it together with the lambda map u
 ``uniform_map`` / ``gradient_map`` / ``view_dependent_map`` / ``roi_map`` build the fixed maps of the
 evaluation scripts (utils.py:436-445, evaluate_view_dep.py:207-260); ``facing_map`` is the second half of the view-dependent
 experiment (evaluate_view_dep.py:354-376): quality by the angle between a point's normal and the viewing ray; ``visibility_map`` goes one step further and scores a point
-by what the judged views can show at all (render.visibility: how far it lies behind the z-buffer front).  Elementwise work
+by what the judged views can show at all (render.visibility: how far it lies behind the z-buffer front); ``distance_map`` scores
+it by how large a camera at a position sees it (render.camera_visibility's depth).  Elementwise work
 on [N, 2] tensors; plain torch.
 """
 import math
@@ -104,6 +105,42 @@ def visibility_map(coords_map, behind, q_g, q_a, tolerance=2, falloff=8, floor=0
     score = visibility_score(behind, tolerance, falloff, floor)
     if score.shape[0] != coords_map.n:
         raise ValueError("visibility map: %d scores for %d coordinates" % (score.shape[0], coords_map.n))
+    score = score.to(coords_map.device)
+    return SparseTensor(torch.stack([float(q_g) * score, float(q_a) * score], dim=1).to(torch.float32).contiguous(), coordinate_map=coords_map)
+
+
+def distance_score(depth, focal, full=1.0, floor=0.0):
+    """float64 [N]: clip((focal * 256 / depth) / full, floor, 1) from ``depth`` (integers: render.camera_visibility's third
+    result, the distance along the viewing direction in 1/256 voxel) and the camera's ``focal`` in pixels.  focal * 256 / depth
+    is the edge of the projected voxel in pixels: a voxel that covers ``full`` pixels or more gets full quality, a smaller one
+    proportionally less, never below ``floor``.  0 wherever depth == render.OFFSCREEN (the camera does not draw the point).
+    Float64 arithmetic on the integer input.
+
+    The defaults (a full pixel, no floor) are starting values, NOT tuned against rate or quality."""
+    from .render import OFFSCREEN
+    focal, full, floor = float(focal), float(full), float(floor)
+    if not (focal > 0 and math.isfinite(focal) and full > 0 and math.isfinite(full)):
+        raise ValueError("distance score: focal and full are positive (got %r, %r)" % (focal, full))
+    if not 0.0 <= floor <= 1.0:
+        raise ValueError("distance score: floor is in [0, 1] (got %r)" % floor)
+    depth = torch.as_tensor(depth)
+    if depth.is_floating_point() or depth.is_complex() or depth.dtype == torch.bool or depth.dim() != 1:
+        raise ValueError("distance score: depth is a one-dimensional integer tensor (render.camera_visibility's third result)")
+    d = depth.to(torch.int64)
+    if bool((d <= 0).any()):
+        raise ValueError("distance score: depths are positive (a drawn point lies beyond the near plane)")
+    score = torch.clamp(((focal * 256.0) / d.to(torch.float64)) / full, min=floor, max=1.0)
+    return torch.where(d == OFFSCREEN, torch.zeros_like(score), score)
+
+
+def distance_map(coords_map, depth, focal, q_g, q_a, full=1.0, floor=0.0):
+    """quality by how large the camera sees a voxel: score = distance_score(depth, focal, ...), channels [q_g * score,
+    q_a * score] (float64 products, cast to float32 — as visibility_map).  ``depth`` must be in the row order of
+    ``coords_map.coords``: ``_, _, depth = render.camera_visibility(coords_map.coords[:, 1:4], [camera])``, ``focal`` is
+    ``camera.focal``."""
+    score = distance_score(depth, focal, full, floor)
+    if score.shape[0] != coords_map.n:
+        raise ValueError("distance map: %d scores for %d coordinates" % (score.shape[0], coords_map.n))
     score = score.to(coords_map.device)
     return SparseTensor(torch.stack([float(q_g) * score, float(q_a) * score], dim=1).to(torch.float32).contiguous(), coordinate_map=coords_map)
 

@@ -18,11 +18,16 @@ orthographic), square integer splats instead of round anti-aliased GL points, an
 ``visibility`` is the way back from such an image to the points (``pcc_view_visibility``): per point, how many voxels it lies
 behind the z-buffer front of the given views and how many pixels show it — what q_map.visibility_map builds its quality map from.
 
+``Camera``, ``render_camera`` and ``camera_visibility`` are the same two operators for a viewer who stands at a point: a pinhole
+camera quantised to integers on the host, a perspective projection in int64 on the device (``pcc_render_camera``,
+``pcc_camera_visibility``), and per point also its depth, which q_map.distance_map turns into a quality map.
+
 ``view_metrics`` restates scikit-image's formulas in float64 (``pcc_image_compare``).  scikit-image is no dependency of
 this project and was not at hand: the ``yuv_from_rgb`` coefficients, the SSIM constants (K1 = 0.01, K2 = 0.03, 7 x 7
 uniform window, sample covariance, crop of 3) and the data-range rule of ``peak_signal_noise_ratio`` are recalled from its
 source, not pinned against it.
 """
+import collections
 import math
 
 import numpy as np
@@ -112,6 +117,19 @@ def colours_to_bytes(rgb):
     return torch.clamp(torch.round(rgb.to(torch.float32) * 255.0), 0.0, 255.0).to(torch.uint8)
 
 
+def _sorted_coords(L, xyz, n, dev):
+    """(batch 0, x, y, z) rows on ``dev`` in canonical (x, y, z) order and the permutation that put them there (None for n < 2)"""
+    coords = torch.cat([torch.zeros((n, 1), dtype=torch.int32, device=dev), xyz.to(dev)], dim=1).contiguous()
+    if n < 2:
+        return coords, None
+    nbytes = L.pcc_sort_scratch_bytes(n)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    perm = torch.empty(n, dtype=torch.int32, device=dev)
+    check(L.pcc_sort_coords(ptr(coords), n, ptr(perm), ptr(scratch), nbytes, _lib.stream()))
+    perm = perm.long()
+    return coords[perm].contiguous(), perm
+
+
 def render_view(cloud, front, up, H, W, frame=None, point_size=None, background=(255, 255, 255), device=None):
     """Render ``cloud`` ([N, 6]: integer x, y, z and r, g, b in [0, 1]; one batch item) from the signed axis ``front`` with
     ``up`` upwards -> uint8 [H, W, 3] tensor on the cloud's device (``device`` for an array; a GPU: there is no CPU renderer).
@@ -139,15 +157,10 @@ def render_view(cloud, front, up, H, W, frame=None, point_size=None, background=
         raise ValueError("background is three bytes")
     bg = bg.astype(np.uint8)
     with torch.cuda.device(dev):
-        coords = torch.cat([torch.zeros((n, 1), dtype=torch.int32, device=dev), xyz.to(dev)], dim=1).contiguous()
+        coords, perm = _sorted_coords(L, xyz, n, dev)  # canonical (x, y, z) order: the tie rule's "lowest row"
         rgb8 = colours_to_bytes(cloud[:, 3:6].to(dev)).contiguous()
-        if n > 1:                                      # canonical (x, y, z) order: the tie rule's "lowest row"
-            nbytes = L.pcc_sort_scratch_bytes(n)
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            perm = torch.empty(n, dtype=torch.int32, device=dev)
-            check(L.pcc_sort_coords(ptr(coords), n, ptr(perm), ptr(scratch), nbytes, _lib.stream()))
-            perm = perm.long()
-            coords, rgb8 = coords[perm].contiguous(), rgb8[perm].contiguous()
+        if perm is not None:
+            rgb8 = rgb8[perm].contiguous()
         zbytes = L.pcc_render_scratch_bytes(int(H), int(W))
         zbuf = torch.empty(max(zbytes, 8), dtype=torch.uint8, device=dev)
         image = torch.empty((int(H), int(W), 3), dtype=torch.uint8, device=dev) if zbytes else None
@@ -209,15 +222,7 @@ def visibility(cloud, views, H, W, frames=None, point_size=None, device=None):
     L = _lib.lib()
     with torch.cuda.device(dev):
         xyz = xyz.to(dev)
-        coords = torch.cat([torch.zeros((n, 1), dtype=torch.int32, device=dev), xyz], dim=1).contiguous()
-        perm = None
-        if n > 1:                                      # canonical (x, y, z) order: the tie rule's "lowest row"
-            nbytes = L.pcc_sort_scratch_bytes(n)
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            perm = torch.empty(n, dtype=torch.int32, device=dev)
-            check(L.pcc_sort_coords(ptr(coords), n, ptr(perm), ptr(scratch), nbytes, _lib.stream()))
-            perm = perm.long()
-            coords = coords[perm].contiguous()
+        coords, perm = _sorted_coords(L, xyz, n, dev)  # canonical (x, y, z) order: the tie rule's "lowest row"
         zbytes = L.pcc_visibility_scratch_bytes(H, W)
         zbuf = torch.empty(max(zbytes, 8), dtype=torch.uint8, device=dev)
         behind = torch.empty(n, dtype=torch.int32, device=dev)
@@ -234,6 +239,217 @@ def visibility(cloud, views, H, W, frames=None, point_size=None, device=None):
         if perm is not None:                           # back to the input's row order
             behind, won = torch.empty_like(behind).index_copy_(0, perm, behind), torch.empty_like(won).index_copy_(0, perm, won)
     return behind, won
+
+
+CameraInts = collections.namedtuple("CameraInts", "pos_q axes_q focal_q near_q H W")
+POS_Q_MAX, AXIS_ONE, FOCAL_Q_MAX = 1 << 24, 1 << 14, 1 << 20            # the limits of include/pcc_hip.h's camera table
+
+
+def _vec3(v, name):
+    a = np.asarray(v, dtype=np.float64)
+    if a.shape != (3,) or not np.isfinite(a).all():
+        raise ValueError("%s must be three finite numbers, got %r" % (name, v))
+    return a
+
+
+def _unit(a, name):
+    length = float(np.sqrt((a * a).sum()))
+    if not length > 0.0:
+        raise ValueError("%s has no direction (zero length)" % name)
+    return a / length
+
+
+class Camera:
+    """A pinhole camera at a position, built in float64 and then QUANTISED: only the integers of ``quantised()`` reach the
+    library (include/pcc_hip.h, ``pcc_render_camera``), so two cameras with equal integers render equal bytes.
+
+    ``front`` points from the scene to the camera (the convention of ``view_axes`` and open3d's ``set_front``); with ``look_at``
+    it is normalise(position - look_at).  right = normalise(up x front), up' = front x right.  ``focal`` is in pixels; with
+    ``fov_y`` (degrees, the full vertical angle) focal = (H / 2) / tan(fov_y / 2).  Exactly one of ``look_at`` / ``front`` and
+    exactly one of ``fov_y`` / ``focal``; ``near`` is the distance of the near plane in voxels.  The principal point is the
+    image centre (W / 2, H / 2).
+
+    Quantisation: pos_q = rint(16 position) (1/16 voxel, |position| <= 2^20), axes_q = rint(2^14 [right; up'; front]) (an
+    axis-aligned camera is exact), focal_q = rint(16 focal) in 1 .. 2^20, near_q = rint(16 near) >= 1, H and W in 1 .. 8192.
+    ValueError for anything outside, and for an ``up`` parallel to ``front``."""
+
+    def __init__(self, position, look_at=None, front=None, up=(0, 1, 0), fov_y=None, focal=None, H=None, W=None, near=1.0):
+        if (look_at is None) == (front is None):
+            raise ValueError("camera: give look_at or front (exactly one of them)")
+        if (fov_y is None) == (focal is None):
+            raise ValueError("camera: give fov_y or focal (exactly one of them)")
+        if H is None or W is None:
+            raise ValueError("camera: the image size H, W is required")
+        H, W = _image_size(H, W)
+        position = _vec3(position, "position")
+        f = _unit(position - _vec3(look_at, "look_at") if look_at is not None else _vec3(front, "front"), "front")
+        right = np.cross(_unit(_vec3(up, "up"), "up"), f)
+        if not float(np.sqrt((right * right).sum())) > 1e-9:
+            raise ValueError("camera: up %r is parallel to front %r" % (up, tuple(f.tolist())))
+        right = _unit(right, "up x front")
+        up2 = np.cross(f, right)
+        if fov_y is not None:
+            fov_y = float(fov_y)
+            if not 0.0 < fov_y < 180.0:
+                raise ValueError("camera: fov_y is an angle in (0, 180) degrees, got %r" % fov_y)
+            focal = (H / 2.0) / math.tan(math.radians(fov_y) / 2.0)
+        focal, near = float(focal), float(near)
+        if not (math.isfinite(focal) and math.isfinite(near)):
+            raise ValueError("camera: focal and near must be finite")
+        axes = np.stack([right, up2, f])
+        self._set(position, axes, focal, near, H, W,
+                  np.rint(16.0 * position), np.rint(float(AXIS_ONE) * axes), np.rint(16.0 * focal), np.rint(16.0 * near))
+
+    def _set(self, position, axes, focal, near, H, W, pos_q, axes_q, focal_q, near_q):
+        pos_q = tuple(int(v) for v in np.asarray(pos_q).reshape(3))
+        axes_q = tuple(tuple(int(v) for v in row) for row in np.asarray(axes_q).reshape(3, 3))
+        focal_q, near_q = int(focal_q), int(near_q)
+        if max(abs(v) for v in pos_q) > POS_Q_MAX:
+            raise ValueError("camera: position beyond +-2^20 voxels")
+        if max(abs(v) for row in axes_q for v in row) > AXIS_ONE:
+            raise ValueError("camera: an axis entry beyond +-2^14")
+        if not 1 <= focal_q <= FOCAL_Q_MAX:
+            raise ValueError("camera: focal must quantise to 1 .. 2^20 sixteenths of a pixel (got %d)" % focal_q)
+        if not 1 <= near_q <= 0x7FFFFFFF:
+            raise ValueError("camera: near must quantise to at least one sixteenth of a voxel (got %d)" % near_q)
+        self.position, self.focal, self.near, self.H, self.W = np.asarray(position, dtype=np.float64), float(focal), float(near), H, W
+        self.right, self.up, self.front = (np.asarray(a, dtype=np.float64) for a in axes)
+        self._ints = CameraInts(pos_q, axes_q, focal_q, near_q, H, W)
+
+    def quantised(self):
+        """-> CameraInts(pos_q (3 ints), axes_q (3 x 3 ints: right, up', front), focal_q, near_q, H, W)"""
+        return self._ints
+
+    @classmethod
+    def from_quantised(cls, pos_q, axes_q, focal_q, near_q, H, W):
+        """the camera with exactly these integers (``Camera.from_quantised(*camera.quantised())`` is ``camera`` again)"""
+        H, W = _image_size(H, W)
+        try:
+            p, a = np.asarray(pos_q), np.asarray(axes_q)
+            exact = (p.shape == (3,) and a.shape == (3, 3) and all(int(v) == v for v in p.tolist() + a.reshape(-1).tolist())
+                     and int(focal_q) == focal_q and int(near_q) == near_q)
+        except (TypeError, ValueError):
+            exact = False
+        if not exact:
+            raise ValueError("camera: from_quantised takes integers: pos_q[3], axes_q[3][3], focal_q, near_q, H, W")
+        self = cls.__new__(cls)
+        self._set(p.astype(np.float64) / 16.0, a.astype(np.float64) / float(AXIS_ONE), focal_q / 16.0, near_q / 16.0, H, W, p, a,
+                  focal_q, near_q)
+        return self
+
+    def __repr__(self):
+        return "Camera.from_quantised(%r, %r, %d, %d, %d, %d)" % tuple(self._ints)
+
+
+def _image_size(H, W):
+    try:
+        h, w = int(H), int(W)
+        ok = h == H and w == W and 1 <= h <= MAX_DIM and 1 <= w <= MAX_DIM
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("H and W must be integers in 1 .. %d (got %r x %r)" % (MAX_DIM, H, W))
+    return h, w
+
+
+def _ps_q(point_size):
+    """rint(16 point_size) for point_size in (0, 16]: the voxel's edge in 1/16 voxel, 1 .. 256"""
+    try:
+        ps = float(point_size)
+    except (TypeError, ValueError):
+        ps = float("nan")
+    q = int(np.rint(16.0 * ps)) if math.isfinite(ps) else 0
+    if not (0.0 < ps <= 16.0 and 1 <= q <= 256):
+        raise ValueError("point_size is a voxel edge in (0, 16] voxels (got %r)" % (point_size,))
+    return q
+
+
+def _camera_args(camera):
+    q = camera.quantised()
+    return np.asarray(q.pos_q, dtype=np.int32), np.asarray(q.axes_q, dtype=np.int32).reshape(9), q
+
+
+def render_camera(cloud, camera, point_size=1.0, background=(255, 255, 255), device=None):
+    """Render ``cloud`` ([N, 6]: integer x, y, z and r, g, b in [0, 1]) as ``camera`` (a ``Camera``) sees it -> uint8 [H, W, 3]
+    tensor on the cloud's device (``device`` for an array; a GPU), H and W the camera's (``pcc_render_camera``).
+
+    Perspective, in integers (include/pcc_hip.h states the projection): a voxel is a square splat of its projected edge
+    ``focal * point_size / depth`` pixels, rounded up and clamped to 1 .. 16, centred on its projection; points nearer than
+    ``camera.near`` (or behind the camera) are not drawn.  A pixel shows the point with the smallest depth key (1/256 voxel);
+    among equal keys the lowest row wins, and rows are put in canonical (x, y, z) order first, so the image does not depend on
+    the input's row order.  ``point_size`` is the voxel's edge in voxels, in (0, 16].  Not a lens: square splats, no
+    anti-aliasing, and holes open between voxels once one projects beyond 16 pixels."""
+    if not isinstance(camera, Camera):
+        raise ValueError("render_camera: camera is a render.Camera, got %r" % (camera,))
+    ps_q = _ps_q(point_size)
+    cloud, xyz = _int_xyz(cloud)
+    if cloud.shape[1] < 6:
+        raise ValueError("a cloud is a [N, 6] array: x, y, z, r, g, b")
+    dev = torch.device(device) if device is not None else (cloud.device if cloud.is_cuda else torch.device("cuda:0"))
+    if dev.type != "cuda":
+        raise ValueError("render_camera runs on the GPU: got device %s" % dev)
+    n = int(cloud.shape[0])
+    if n and int(xyz.abs().max()) > COORD_LIMIT:
+        raise ValueError("render_camera: coordinates beyond +-%d" % COORD_LIMIT)
+    bg = np.asarray(background)
+    if bg.shape != (3,) or bg.min() < 0 or bg.max() > 255:
+        raise ValueError("background is three bytes")
+    bg = bg.astype(np.uint8)
+    pos, axes, q = _camera_args(camera)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        coords, perm = _sorted_coords(L, xyz, n, dev)
+        rgb8 = colours_to_bytes(cloud[:, 3:6].to(dev)).contiguous()
+        if perm is not None:
+            rgb8 = rgb8[perm].contiguous()
+        zbytes = L.pcc_render_scratch_bytes(q.H, q.W)
+        zbuf = torch.empty(max(zbytes, 8), dtype=torch.uint8, device=dev)
+        image = torch.empty((q.H, q.W, 3), dtype=torch.uint8, device=dev)
+        check(L.pcc_render_camera(ptr(coords) if n else None, ptr(rgb8) if n else None, n, ptr(pos), ptr(axes), q.focal_q, q.near_q,
+                                  q.H, q.W, ps_q, ptr(bg), ptr(zbuf), zbytes, ptr(image), _lib.stream()))
+    return image
+
+
+def camera_visibility(cloud, cameras, point_size=1.0, device=None):
+    """Which points do ``cameras`` (a non-empty list of ``Camera``) show?  -> (behind, won, depth): int32 [N] tensors on the GPU
+    in the INPUT's row order (``pcc_camera_visibility``).
+
+    For one camera, with the projection, clipping and winner rule of ``render_camera``: ``behind[i]`` is the minimum over the
+    pixels of point i's splat inside the image of (its depth key - the pixel's front depth key) >> 8: whole voxels behind what
+    the camera sees, 0 within one voxel of the front; ``won[i]`` the number of pixels that show point i; ``depth[i]`` its depth
+    key, the distance along the viewing direction in 1/256 voxel (what q_map.distance_score reads).  A point that is not drawn
+    (nearer than ``near``, behind the camera) or whose splat lies wholly outside the image has behind = depth = ``OFFSCREEN``
+    and won = 0.  Over several cameras: minimum, sum, minimum.  ``behind`` feeds q_map.visibility_score / visibility_map as
+    ``visibility``'s does.  All integer and bitwise reproducible."""
+    if isinstance(cameras, Camera) or not isinstance(cameras, (list, tuple)):
+        raise ValueError("cameras is a list of render.Camera, got %r" % (cameras,))
+    if len(cameras) == 0:
+        raise ValueError("cameras is empty: camera_visibility needs at least one camera")
+    if any(not isinstance(c, Camera) for c in cameras):
+        raise ValueError("cameras is a list of render.Camera, got %r" % (cameras,))
+    ps_q = _ps_q(point_size)
+    cloud, xyz = _int_xyz(cloud)
+    dev = torch.device(device) if device is not None else (cloud.device if cloud.is_cuda else torch.device("cuda:0"))
+    if dev.type != "cuda":
+        raise ValueError("camera_visibility runs on the GPU: got device %s" % dev)
+    n = int(cloud.shape[0])
+    if n and int(xyz.abs().max()) > COORD_LIMIT:
+        raise ValueError("camera_visibility: coordinates beyond +-%d" % COORD_LIMIT)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        behind, won, depth = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+        if n == 0:
+            return behind, won, depth
+        coords, perm = _sorted_coords(L, xyz, n, dev)
+        zbytes = max(L.pcc_render_scratch_bytes(c.H, c.W) for c in cameras)
+        zbuf = torch.empty(max(zbytes, 8), dtype=torch.uint8, device=dev)
+        for k, camera in enumerate(cameras):
+            pos, axes, q = _camera_args(camera)
+            check(L.pcc_camera_visibility(ptr(coords), n, ptr(pos), ptr(axes), q.focal_q, q.near_q, q.H, q.W, ps_q, ptr(zbuf), zbytes,
+                                          int(k > 0), ptr(behind), ptr(won), ptr(depth), _lib.stream()))
+        if perm is not None:                           # back to the input's row order
+            behind, won, depth = (torch.empty_like(t).index_copy_(0, perm, t) for t in (behind, won, depth))
+    return behind, won, depth
 
 
 def data_range_of(ref_min):

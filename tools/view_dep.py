@@ -14,7 +14,10 @@ usage: view_dep.py [config1 | config2 | frame.ply] [--out DIR] [--view front|sid
                    points' normals and the viewing direction)
                    [--visibility [--vis-views front side] [--vis-tolerance 2] [--vis-falloff 8] [--vis-floor 0.0]]     (a row
                    "visible": quality by how far a point lies behind what the views show, render.visibility; --vis-views are names
-                   of the active view table, the judged view when left out)"""
+                   of the active view table, the judged view when left out)
+                   [--camera X,Y,Z --look-at X,Y,Z --fov 30]     (a pinhole camera at a position in place of the axis view:
+                   every image is render.render_camera's at --height x --width, --fov the full vertical angle in degrees; --look-at
+                   defaults to the middle of the frame's bounding box; --visibility then asks render.camera_visibility of this camera)"""
 import argparse
 import csv
 import json
@@ -28,6 +31,13 @@ import torch  # noqa: E402
 import pcc_amd  # noqa: E402,F401
 from pcc_amd import io, render, synthetic as syn  # noqa: E402
 from pcc_amd.harness import evaluate_view_dependent  # noqa: E402
+
+
+def xyz(text):
+    parts = text.split(",")
+    if len(parts) != 3:
+        raise argparse.ArgumentTypeError("three comma-separated numbers, got %r" % text)
+    return tuple(float(v) for v in parts)
 
 
 def main():
@@ -54,6 +64,9 @@ def main():
     ap.add_argument("--vis-tolerance", type=int, default=2)
     ap.add_argument("--vis-falloff", type=int, default=8)
     ap.add_argument("--vis-floor", type=float, default=0.0)
+    ap.add_argument("--camera", type=xyz, metavar="X,Y,Z", help="judge from a pinhole camera at this position instead of the axis view")
+    ap.add_argument("--look-at", type=xyz, metavar="X,Y,Z", help="the point the camera looks at (default: the middle of the bounding box)")
+    ap.add_argument("--fov", type=float, default=30.0, help="the camera's full vertical field of view in degrees")
     ap.add_argument("--repeat", type=int, default=0, help="time render_view and view_metrics over N further calls")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
@@ -76,14 +89,24 @@ def main():
     details = {}
     facing = {"radius": a.facing_radius, "floor": a.facing_floor} if a.facing else None
     visibility = None
-    if a.visibility:
+    camera = None
+    if a.look_at is not None and a.camera is None:
+        ap.error("--look-at needs --camera")
+    if a.camera is not None:
+        if a.vis_views:
+            ap.error("--vis-views are axis views: with --camera the visibility is the camera's")
+        look_at = a.look_at if a.look_at is not None else tuple(((pts[:, :3].min(axis=0) + pts[:, :3].max(axis=0)) / 2.0).tolist())
+        camera = render.Camera(a.camera, look_at=look_at, up=(0, 0, 1) if a.mvub else (0, 1, 0), fov_y=a.fov, H=a.height, W=a.width)
+        if a.visibility:
+            visibility = {"tolerance": a.vis_tolerance, "falloff": a.vis_falloff, "floor": a.vis_floor}
+    elif a.visibility:
         table = render.VIEWS_MVUB if a.mvub else render.VIEWS
         visibility = {"views": [table[name] for name in (a.vis_views or [a.view])], "tolerance": a.vis_tolerance, "falloff": a.vis_falloff,
                       "floor": a.vis_floor}
     t0 = time.time()
     rows = evaluate_view_dependent(a.experiment, model, data, a.q_a, a.q_g, dev, a.out, view=view if a.mvub else a.view, H=a.height,
                                    W=a.width, gradient=gradient, roi=roi, save_images=True, details=details, facing=facing,
-                                   visibility=visibility)
+                                   visibility=visibility, camera=camera)
     t_all = time.time() - t0
     path = os.path.join(a.out, a.experiment, "view_dep.csv")
     with open(path, "w", newline="") as f:
@@ -94,18 +117,23 @@ def main():
     for key, row in rows.items():
         print("%-8s bpp %.4f  view psnr %.3f dB  view ssim %.5f" % (key, row["bpp"], row["psnr"], row["ssim"]))
     result = {"frame": a.frame, "n_points": int(pts.shape[0]), "H": a.height, "W": a.width, "view": a.view, "t_three_rows_s": t_all}
+    if camera is not None:
+        result["view"] = "camera"
+        q = camera.quantised()
+        result["camera"] = {"position": list(a.camera), "look_at": list(look_at), "fov_y": a.fov, "pos_q": list(q.pos_q),
+                            "axes_q": [list(r) for r in q.axes_q], "focal_q": q.focal_q, "near_q": q.near_q}
     if a.facing or a.visibility:
         result["t_%s_rows_s" % {4: "four", 5: "five"}[len(rows)]] = result.pop("t_three_rows_s")
     if a.visibility:
         behind = details["visibility"][0]
-        result["visibility"] = {"views": a.vis_views or [a.view], "tolerance": a.vis_tolerance, "falloff": a.vis_falloff, "floor": a.vis_floor,
+        result["visibility"] = {"views": ["camera"] if camera is not None else (a.vis_views or [a.view]), "tolerance": a.vis_tolerance, "falloff": a.vis_falloff, "floor": a.vis_floor,
                                 "on_front": int((behind == 0).sum()), "within_tolerance": int((behind <= a.vis_tolerance).sum()),
                                 "offscreen": int((behind == render.OFFSCREEN).sum())}
     if a.repeat > 0:
         src, ref_img = details["source"]
         rec, img = details["uniform"]
         front, up = view
-        frame = render.view_frame(src, front, up, a.height, a.width)
+        frame = None if camera is not None else render.view_frame(src, front, up, a.height, a.width)
 
         def timed(fn):
             fn()
@@ -116,9 +144,12 @@ def main():
             torch.cuda.synchronize()
             return (time.time() - t) / a.repeat * 1e3
 
-        result["render_view_ms"] = timed(lambda: render.render_view(rec, front, up, a.height, a.width, frame=frame))
+        if camera is not None:
+            result["render_camera_ms"] = timed(lambda: render.render_camera(rec, camera))
+        else:
+            result["render_view_ms"] = timed(lambda: render.render_view(rec, front, up, a.height, a.width, frame=frame))
+            result["scale"] = frame[4]
         result["view_metrics_ms"] = timed(lambda: render.view_metrics(ref_img, img))
-        result["scale"] = frame[4]
     print(json.dumps(result))
     print("wrote", path)
 
