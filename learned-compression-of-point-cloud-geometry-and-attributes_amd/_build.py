@@ -35,9 +35,10 @@ NO_SCRATCH = {
     # the perceptual metric (csrc/pcqm.hip): 20 running sums per point live through up to 4,218 probes and gathers; a spilled
     # one would put a scratch round trip behind every neighbour.  The kappa kernel shares the normals' Jacobi over named scalars
     "pcqm": ("surface_variation_kernel", "pcqm_features_kernel"),
-    # the camera views (csrc/render.hip): three emulated 64-bit divisions per point sit in front of up to 256 atomics or reads;
-    # a spill among their operands would be a scratch round trip per point in two kernels that otherwise touch only the z-buffer
-    "render": ("camera_splat_kernel", "camera_gather_kernel"),
+    # the views (csrc/render.hip; the two templates, so both instantiations of each, orthographic and camera): three emulated
+    # 64-bit divisions per point of a camera view sit in front of up to 256 atomics or reads; a spill among their operands would
+    # be a scratch round trip per point in two kernels that otherwise touch only the z-buffer
+    "render": ("splat_kernel", "gather_kernel"),
 }
 
 
@@ -152,8 +153,9 @@ def check_kernel_resources(path=None, kernels=None):
     bad = {k: v for k, v in seen.items() if any(t in k for t in kernels)
            and (v.get("ScratchSize [bytes/lane]", 0) or v.get("SGPRs Spill", 0) or v.get("VGPRs Spill", 0))}
     checked = [k for k in seen if any(t in k for t in kernels)]
-    if not checked:
-        raise RuntimeError(f"{path}: no resource remarks for {kernels} (compiler flag dropped?)")
+    unmatched = [t for t in kernels if not any(t in k for k in seen)]
+    if unmatched:
+        raise RuntimeError(f"{path}: no resource remarks for {unmatched} (kernel renamed, or compiler flag dropped?)")
     if bad:
         raise RuntimeError(f"kernels with scratch memory or spills (must be none): {bad}")
     return {k: (seen[k].get("VGPRs"), seen[k].get("ScratchSize [bytes/lane]")) for k in checked}

@@ -7,22 +7,23 @@
 //
 //   u = right . p, v = up . p, d = front . p              (front points from the object to the camera, as open3d's set_front)
 //   the point covers columns (u - u_min) scale + ox + i and rows (v_max - v) scale + oy + j,  i, j in [0, point_size)
-//   pixels outside the image are dropped one by one; the pixel shows the point with the largest d and, among equal d,
-//   the lowest row index; untouched pixels show the background
+//   pixels outside the image are dropped; the pixel shows the point with the largest d and, among equal d, the lowest row
+//   index; untouched pixels show the background
 //
-// Three kernels: the z-buffer is cleared to 0; one thread per point does point_size^2 64-bit atomicMax of the word
-// ((d + 2^18) << 32) | (0xFFFFFFFF - row); one thread per four pixels resolves the words to colours.  A maximum does not depend
-// on the order its operands arrive in, so the image is bitwise reproducible although the splat is atomic.  |d| <= COORD_LIMIT
-// < 2^18, so d + 2^18 is positive and the word of a drawn pixel is never 0; a row with a coordinate outside the range draws
-// nothing.  Atomic bound: n point_size^2 64-bit atomics on H W words.
+// One z-buffer for every kind of view.  A view type (RenderView, CameraView) projects a row to a Splat: its square clipped to
+// the image and a 31-bit key, larger = nearer.  Three kernels: the z-buffer is cleared to 0; splat_kernel<View>, one thread per
+// point, does one 64-bit atomicMax of the word (key << 32) | (0xFFFFFFFF - row) per pixel of the splat; one thread per four
+// pixels resolves the words to colours.  A maximum does not depend on the order its operands arrive in, so the image is bitwise
+// reproducible although the splat is atomic.  Every key is positive, so the word of a drawn pixel is never 0; a row with a
+// coordinate outside the range draws nothing.  Atomic bound: at most 16 x 16 64-bit atomics per point on H W words.
 //
-// pcc_view_visibility is the way back from the pixels to the points: the same clear and splat, then one thread per point walks
-// its splat again and reads how far the point lies behind the z-buffer front (`behind`, the minimum over its pixels) and how
-// many pixels it owns (`won`).  No image is resolved.
+// pcc_view_visibility is the way back from the pixels to the points: the same clear and splat, then gather_kernel<View>, one
+// thread per point, walks its splat again and reads how far the point lies behind the z-buffer front (`behind`, the minimum over
+// its pixels of (front key - own key) >> View::GAP_SHIFT) and how many pixels it owns (`won`).  No image is resolved.
 //
-// pcc_render_camera and pcc_camera_visibility are the same two operators for a pinhole camera at a position: a perspective
-// projection in int64 (camera_project below) between the shared clear and resolve kernels, and a walk back that also
-// returns each point's depth.
+// pcc_render_view and pcc_view_visibility use the orthographic RenderView (key = d + 2^18, gap shift 0: whole voxels);
+// pcc_render_camera and pcc_camera_visibility the pinhole CameraView at a position (a perspective projection in int64, key =
+// 0x7FFFFFFF - depth key in 1/256 voxel, gap shift 8), whose walk back also returns each point's depth key.
 //
 // pcc_image_compare replaces rgb2yuv +peak_signal_noise_ratio + structural_similarity (evaluate_view_dep.py:196-204) by
 // their raw sums in float64: one workgroup per IC_TILE x IC_TILE tile converts the tile and its 6-pixel apron to YUV one
@@ -37,9 +38,87 @@ namespace pcc {
 constexpr int RENDER_DEPTH_BIAS = 1 << 18;
 constexpr int RENDER_MAX_DIM = 8192;
 
+// One projected point: its splat clipped to the image (rows r0 .. r1 - 1, columns c0 .. c1 - 1) and the high half of its
+// z-buffer word, in (0, 2^31): the larger key is the nearer point.
+struct Splat {
+    int32_t r0, r1, c0, c1;
+    uint32_t key;
+};
+
+// the square of `size` pixels whose top-left pixel is (row0, col0), clipped to the H x W image once, in int64
+__device__ __forceinline__ void clip_splat(int64_t row0, int64_t col0, int64_t size, int32_t H, int32_t W, Splat& out) {
+    const int64_t c0 = col0 < 0 ? 0 : col0, c1 = col0 + size > W ? W : col0 + size;
+    const int64_t r0 = row0 < 0 ? 0 : row0, r1 = row0 + size > H ? H : row0 + size;
+    // an empty range is stored as 0 .. 0: the clipped bounds of a splat far outside the image do not fit 32 bits
+    const bool inside = c0 < c1 && r0 < r1;
+    out.c0 = inside ? (int32_t)c0 : 0; out.c1 = inside ? (int32_t)c1 : 0;
+    out.r0 = inside ? (int32_t)r0 : 0; out.r1 = inside ? (int32_t)r1 : 0;
+}
+
+__device__ __forceinline__ uint64_t splat_word(uint32_t key, int64_t row) {
+    return ((uint64_t)key << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)row);
+}
+
+// ---- orthographic axis view ----
+// |d| <= COORD_LIMIT < 2^18, so the key d + 2^18 is positive; keys are whole voxels, so the gap between two of them is `behind`.
 struct RenderView {
+    static constexpr int GAP_SHIFT = 0;
+    static constexpr bool HAS_DEPTH = false;
     int32_t r[3], u[3], f[3];
     int32_t u_min, v_max, ox, oy, scale, point_size, H, W;
+
+    // false when the row draws nothing: a coordinate out of range
+    __device__ __forceinline__ bool project(const int4 c, Splat& out) const {
+        if (!coord_in_range(0, c.y, c.z, c.w)) return false;
+        const int pu = r[0] * c.y + r[1] * c.z + r[2] * c.w;
+        const int pv = u[0] * c.y + u[1] * c.z + u[2] * c.w;
+        const int d = f[0] * c.y + f[1] * c.z + f[2] * c.w;
+        // 64-bit positions: u_min / v_max / ox / oy are the caller's and may be anywhere in int32, so (pu - u_min) * scale + ox
+        // reaches about 2^38; the box is narrowed to 32 bits only after it is clipped
+        clip_splat(((int64_t)v_max - pv) * scale + oy, ((int64_t)pu - u_min) * scale + ox, point_size, H, W, out);
+        out.key = (uint32_t)(d + RENDER_DEPTH_BIAS);
+        return true;
+    }
+};
+
+// ---- pinhole camera: perspective projection, all int64 ----
+// The camera crosses the ABI as integers only (pcc_hip.h): pos in 1/16 voxel, the three axes in 2^-14, focal in 1/16 pixel,
+// near in 1/16 voxel, the voxel edge ps in 1/16 voxel.  For a row p:
+//   e = 16 p - pos;  U = right . e, V = up . e, D = -(front . e)   (2^-18 voxel; front points from the scene to the camera)
+//   drawn <=> D >= near 2^14;  X = floor(focal U / D), Y = floor(focal V / D)   (1/16 pixel from the principal point)
+//   s = clamp(ceil(focal ps 2^10 / D), 1, 16);  col0 = floor((8 W + X - 8 s) / 16), row0 = floor((8 H - Y - 8 s) / 16)
+//   depth key dk = D >> 10 (1/256 voxel); key = 0x7FFFFFFF - dk, so the gap between two keys >> 8 is `behind` in whole voxels
+// Bounds, which the host entry re-derives from the arguments it is given (check_camera): |e_k| <= |pos_k| + 16 COORD_LIMIT <
+// 2^24 + 2^21, an axis row has entries of at most 2^14, so |U|, |V|, |D| < 3 2^14 (2^24 + 2^21) < 2^40, |focal U| < 2^60, dk <
+// 2^30 and dk >= 16 near >= 16: the key of a drawn point is in (2^30, 2^31) and never 0.
+
+// floor(a / b) for b > 0, through one unsigned division (C++'s `/` truncates towards zero)
+__device__ __forceinline__ int64_t camera_floordiv(int64_t a, uint64_t b) {
+    return a >= 0 ? (int64_t)((uint64_t)a / b) : -(int64_t)(((uint64_t)(-a) + b - 1) / b);
+}
+
+struct CameraView {
+    static constexpr int GAP_SHIFT = 8;
+    static constexpr bool HAS_DEPTH = true;
+    int32_t pos[3], ax[3][3];
+    int32_t focal, near, ps, H, W;
+
+    // false when the row draws nothing: a coordinate out of range, or in front of the near plane (behind the camera included)
+    __device__ __forceinline__ bool project(const int4 c, Splat& out) const {
+        if (!coord_in_range(0, c.y, c.z, c.w)) return false;
+        const int64_t e0 = 16 * (int64_t)c.y - pos[0], e1 = 16 * (int64_t)c.z - pos[1], e2 = 16 * (int64_t)c.w - pos[2];
+        const int64_t U = ax[0][0] * e0 + ax[0][1] * e1 + ax[0][2] * e2;
+        const int64_t V = ax[1][0] * e0 + ax[1][1] * e1 + ax[1][2] * e2;
+        const int64_t D = -(ax[2][0] * e0 + ax[2][1] * e1 + ax[2][2] * e2);
+        if (D < ((int64_t)near << 14)) return false;
+        const uint64_t d = (uint64_t)D;
+        const int64_t X = camera_floordiv((int64_t)focal * U, d), Y = camera_floordiv((int64_t)focal * V, d);
+        const uint64_t edge = ((((uint64_t)focal * (uint64_t)ps) << 10) + d - 1) / d;
+        const int64_t s = edge < 1 ? 1 : (edge > 16 ? 16 : (int64_t)edge);
+        clip_splat((8 * (int64_t)H - Y - 8 * s) >> 4, (8 * (int64_t)W + X - 8 * s) >> 4, s, H, W, out);   // >> floors
+        out.key = 0x7FFFFFFFu - (uint32_t)(d >> 10);
+        return true;
+    }
 };
 
 __global__ __launch_bounds__(256) void render_clear_kernel(uint64_t* __restrict__ zbuf, int64_t npix) {
@@ -47,27 +126,18 @@ __global__ __launch_bounds__(256) void render_clear_kernel(uint64_t* __restrict_
     if (i < npix) zbuf[i] = 0ull;
 }
 
-__global__ __launch_bounds__(256) void render_splat_kernel(const int32_t* __restrict__ coords, int64_t n, RenderView a,
-                                                           uint64_t* __restrict__ zbuf) {
+// one thread per point, at most 16 x 16 atomics each; the splat is clipped first, so every index is inside H W
+template <class View>
+__global__ __launch_bounds__(256) void splat_kernel(const int32_t* __restrict__ coords, int64_t n, View a, uint64_t* __restrict__ zbuf) {
     const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (row >= n) return;
     const int4 c = reinterpret_cast<const int4*>(coords)[row];                  // (batch, x, y, z): the batch is ignored
-    if (!coord_in_range(0, c.y, c.z, c.w)) return;
-    const int u = a.r[0] * c.y + a.r[1] * c.z + a.r[2] * c.w;
-    const int v = a.u[0] * c.y + a.u[1] * c.z + a.u[2] * c.w;
-    const int d = a.f[0] * c.y + a.f[1] * c.z + a.f[2] * c.w;
-    const uint64_t word = ((uint64_t)(uint32_t)(d + RENDER_DEPTH_BIAS) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)row);
-    // 64-bit positions: (u - u_min) * scale stays below 2^19 * 64, but u_min / ox / oy are the caller's
-    const int64_t px0 = ((int64_t)u - a.u_min) * a.scale + a.ox, py0 = ((int64_t)a.v_max - v) * a.scale + a.oy;
-    for (int j = 0; j < a.point_size; ++j) {
-        const int64_t py = py0 + j;
-        if (py < 0 || py >= a.H) continue;
-        for (int i = 0; i < a.point_size; ++i) {
-            const int64_t px = px0 + i;
-            if (px < 0 || px >= a.W) continue;
-            atomicMax(reinterpret_cast<unsigned long long*>(zbuf) + (py * a.W + px), (unsigned long long)word);
-        }
-    }
+    Splat sp;
+    if (!a.project(c, sp)) return;
+    const uint64_t word = splat_word(sp.key, row);
+    for (int32_t py = sp.r0; py < sp.r1; ++py)
+        for (int32_t px = sp.c0; px < sp.c1; ++px)
+            atomicMax(reinterpret_cast<unsigned long long*>(zbuf) + ((int64_t)py * a.W + px), (unsigned long long)word);
 }
 
 // four pixels (12 bytes = three aligned words of the image) per thread
@@ -98,31 +168,28 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(const uint64_t* __r
 
 // ---- visibility: the way back from the z-buffer's pixels to the points ----
 // One thread per point walks the point's splat again, over the z-buffer the splat kernel has finished: behind = the smallest
-// (d of the pixel's winner) - (d of this point) over its pixels inside the image, won = the pixels whose word is this row's own.
-// Every pixel of the splat holds a word of depth >= d (this row took part in its maximum), so behind >= 0, and it is 0 exactly
-// where the front depth of a pixel is this point's; the tie to the lowest row decides only `won`.  A thread owns its row's two
-// outputs: no atomics, and `accumulate` is a plain read-modify-write (min of behind, sum of won).
-__global__ __launch_bounds__(256) void visibility_gather_kernel(const int32_t* __restrict__ coords, int64_t n, RenderView a,
-                                                                const uint64_t* __restrict__ zbuf, int accumulate,
-                                                                int32_t* __restrict__ behind, int32_t* __restrict__ won) {
+// ((key of the pixel's winner) - (key of this point)) >> View::GAP_SHIFT over its pixels inside the image, won = the pixels whose
+// word is this row's own, depth (View::HAS_DEPTH only, decided at compile time) = 0x7FFFFFFF - key, the point's depth key.
+// Every pixel of the splat holds a word of key >= this row's (it took part in the maximum), so behind >= 0, and it is 0 exactly
+// where the front of a pixel is less than one voxel in front of this point (at its own depth, for the orthographic view); the tie
+// to the lowest row decides only `won`.  A thread owns its row's outputs: no atomics, and `accumulate` is a plain
+// read-modify-write (min of behind and depth, sum of won).
+template <class View>
+__global__ __launch_bounds__(256) void gather_kernel(const int32_t* __restrict__ coords, int64_t n, View a, const uint64_t* __restrict__ zbuf,
+                                                     int accumulate, int32_t* __restrict__ behind, int32_t* __restrict__ won,
+                                                     int32_t* __restrict__ depth) {
     const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (row >= n) return;
     const int4 c = reinterpret_cast<const int4*>(coords)[row];
-    int32_t best = PCC_VIS_OFFSCREEN, count = 0;
-    if (coord_in_range(0, c.y, c.z, c.w)) {
-        const int u = a.r[0] * c.y + a.r[1] * c.z + a.r[2] * c.w;
-        const int v = a.u[0] * c.y + a.u[1] * c.z + a.u[2] * c.w;
-        const int d = a.f[0] * c.y + a.f[1] * c.z + a.f[2] * c.w;
-        const uint64_t own = ((uint64_t)(uint32_t)(d + RENDER_DEPTH_BIAS) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)row);
-        const int64_t px0 = ((int64_t)u - a.u_min) * a.scale + a.ox, py0 = ((int64_t)a.v_max - v) * a.scale + a.oy;
-        for (int j = 0; j < a.point_size; ++j) {
-            const int64_t py = py0 + j;
-            if (py < 0 || py >= a.H) continue;
-            for (int i = 0; i < a.point_size; ++i) {
-                const int64_t px = px0 + i;
-                if (px < 0 || px >= a.W) continue;
-                const uint64_t word = zbuf[py * a.W + px];
-                const int32_t gap = (int32_t)(uint32_t)(word >> 32) - RENDER_DEPTH_BIAS - d;     // 0 .. 2 COORD_LIMIT
+    int32_t best = PCC_VIS_OFFSCREEN, count = 0, dist = PCC_VIS_OFFSCREEN;
+    Splat sp;
+    if (a.project(c, sp) && sp.r0 < sp.r1) {
+        const uint64_t own = splat_word(sp.key, row);
+        dist = (int32_t)(0x7FFFFFFFu - sp.key);
+        for (int32_t py = sp.r0; py < sp.r1; ++py) {
+            for (int32_t px = sp.c0; px < sp.c1; ++px) {
+                const uint64_t word = zbuf[(int64_t)py * a.W + px];
+                const int32_t gap = (int32_t)(((uint32_t)(word >> 32) - sp.key) >> View::GAP_SHIFT);
                 best = gap < best ? gap : best;
                 count += word == own;
             }
@@ -135,108 +202,13 @@ __global__ __launch_bounds__(256) void visibility_gather_kernel(const int32_t* _
     }
     behind[row] = best;
     won[row] = count;
-}
-
-// ---- pinhole camera: perspective splat and walk back, all int64 ----
-// The camera crosses the ABI as integers only (pcc_hip.h): pos in 1/16 voxel, the three axes in 2^-14, focal in 1/16 pixel,
-// near in 1/16 voxel, the voxel edge ps in 1/16 voxel.  For a row p:
-//   e = 16 p - pos;  U = right . e, V = up . e, D = -(front . e)   (2^-18 voxel; front points from the scene to the camera)
-//   drawn <=> D >= near 2^14;  X = floor(focal U / D), Y = floor(focal V / D)   (1/16 pixel from the principal point)
-//   s = clamp(ceil(focal ps 2^10 / D), 1, 16);  col0 = floor((8 W + X - 8 s) / 16), row0 = floor((8 H - Y - 8 s) / 16)
-//   depth key dk = D >> 10 (1/256 voxel); the z-buffer word is ((0x7FFFFFFF - dk) << 32) | (0xFFFFFFFF - row)
-// Bounds, which the host entry re-derives from the arguments it is given (camera_check): |e_k| <= |pos_k| + 16 COORD_LIMIT <
-// 2^24 + 2^21, an axis row has entries of at most 2^14, so |U|, |V|, |D| < 3 2^14 (2^24 + 2^21) < 2^40, |focal U| < 2^60, dk <
-// 2^30 and dk >= 16 near >= 16: the high half of a drawn pixel's word is in (2^30, 2^31) and never 0.  The clear and resolve
-// kernels above are shared with the orthographic view: the word layout is theirs, the larger word is the nearer point and,
-// among equal dk, the lower row.
-struct CameraView {
-    int32_t pos[3], ax[3][3];
-    int32_t focal, near, ps, H, W;
-};
-
-struct CameraSplat {                 // the splat of one point clipped to the image: rows r0 .. r1 - 1, columns c0 .. c1 - 1
-    int32_t r0, r1, c0, c1;
-    uint32_t dk;
-};
-
-// floor(a / b) for b > 0, through one unsigned division (C++'s `/` truncates towards zero)
-__device__ __forceinline__ int64_t camera_floordiv(int64_t a, uint64_t b) {
-    return a >= 0 ? (int64_t)((uint64_t)a / b) : -(int64_t)(((uint64_t)(-a) + b - 1) / b);
-}
-
-// false when the row draws nothing: a coordinate out of range, or in front of the near plane (behind the camera included)
-__device__ __forceinline__ bool camera_project(const int4 c, const CameraView& a, CameraSplat& out) {
-    if (!coord_in_range(0, c.y, c.z, c.w)) return false;
-    const int64_t e0 = 16 * (int64_t)c.y - a.pos[0], e1 = 16 * (int64_t)c.z - a.pos[1], e2 = 16 * (int64_t)c.w - a.pos[2];
-    const int64_t U = a.ax[0][0] * e0 + a.ax[0][1] * e1 + a.ax[0][2] * e2;
-    const int64_t V = a.ax[1][0] * e0 + a.ax[1][1] * e1 + a.ax[1][2] * e2;
-    const int64_t D = -(a.ax[2][0] * e0 + a.ax[2][1] * e1 + a.ax[2][2] * e2);
-    if (D < ((int64_t)a.near << 14)) return false;
-    const uint64_t d = (uint64_t)D;
-    const int64_t X = camera_floordiv((int64_t)a.focal * U, d), Y = camera_floordiv((int64_t)a.focal * V, d);
-    const uint64_t edge = ((((uint64_t)a.focal * (uint64_t)a.ps) << 10) + d - 1) / d;
-    const int64_t s = edge < 1 ? 1 : (edge > 16 ? 16 : (int64_t)edge);
-    const int64_t col0 = (8 * (int64_t)a.W + X - 8 * s) >> 4, row0 = (8 * (int64_t)a.H - Y - 8 * s) >> 4;   // >> floors
-    const int64_t c0 = col0 < 0 ? 0 : col0, c1 = col0 + s > a.W ? a.W : col0 + s;
-    const int64_t r0 = row0 < 0 ? 0 : row0, r1 = row0 + s > a.H ? a.H : row0 + s;
-    out.dk = (uint32_t)(d >> 10);
-    // an empty range is stored as 0 .. 0: the clipped bounds of a splat far outside the image do not fit 32 bits
-    const bool inside = c0 < c1 && r0 < r1;
-    out.c0 = inside ? (int32_t)c0 : 0; out.c1 = inside ? (int32_t)c1 : 0;
-    out.r0 = inside ? (int32_t)r0 : 0; out.r1 = inside ? (int32_t)r1 : 0;
-    return true;
-}
-
-__device__ __forceinline__ uint64_t camera_word(uint32_t dk, int64_t row) {
-    return ((uint64_t)(0x7FFFFFFFu - dk) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)row);
-}
-
-// one thread per point, at most 16 x 16 atomics each
-__global__ __launch_bounds__(256) void camera_splat_kernel(const int32_t* __restrict__ coords, int64_t n, CameraView a,
-                                                           uint64_t* __restrict__ zbuf) {
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (row >= n) return;
-    const int4 c = reinterpret_cast<const int4*>(coords)[row];                  // (batch, x, y, z): the batch is ignored
-    CameraSplat sp;
-    if (!camera_project(c, a, sp)) return;
-    const uint64_t word = camera_word(sp.dk, row);
-    for (int32_t py = sp.r0; py < sp.r1; ++py)
-        for (int32_t px = sp.c0; px < sp.c1; ++px)
-            atomicMax(reinterpret_cast<unsigned long long*>(zbuf) + ((int64_t)py * a.W + px), (unsigned long long)word);
-}
-
-// the way back, as visibility_gather_kernel: behind in whole voxels (dk differences >> 8), won, and the point's own depth key
-__global__ __launch_bounds__(256) void camera_gather_kernel(const int32_t* __restrict__ coords, int64_t n, CameraView a,
-                                                            const uint64_t* __restrict__ zbuf, int accumulate,
-                                                            int32_t* __restrict__ behind, int32_t* __restrict__ won,
-                                                            int32_t* __restrict__ depth) {
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (row >= n) return;
-    const int4 c = reinterpret_cast<const int4*>(coords)[row];
-    int32_t best = PCC_VIS_OFFSCREEN, count = 0, dist = PCC_VIS_OFFSCREEN;
-    CameraSplat sp;
-    if (camera_project(c, a, sp) && sp.r0 < sp.r1) {
-        const uint64_t own = camera_word(sp.dk, row);
-        dist = (int32_t)sp.dk;
-        for (int32_t py = sp.r0; py < sp.r1; ++py) {
-            for (int32_t px = sp.c0; px < sp.c1; ++px) {
-                const uint64_t word = zbuf[(int64_t)py * a.W + px];
-                const uint32_t dk_front = 0x7FFFFFFFu - (uint32_t)(word >> 32);     // <= dk: this row took part in the maximum
-                const int32_t gap = (int32_t)((sp.dk - dk_front) >> 8);
-                best = gap < best ? gap : best;
-                count += word == own;
-            }
+    if constexpr (View::HAS_DEPTH) {
+        if (accumulate) {
+            const int32_t old = depth[row];
+            dist = old < dist ? old : dist;
         }
+        depth[row] = dist;
     }
-    if (accumulate) {
-        const int32_t old_b = behind[row], old_d = depth[row];
-        best = old_b < best ? old_b : best;
-        dist = old_d < dist ? old_d : dist;
-        count += won[row];
-    }
-    behind[row] = best;
-    won[row] = count;
-    depth[row] = dist;
 }
 
 // ---- image metrics ----
@@ -345,6 +317,14 @@ static bool signed_unit_axis(const int32_t* a) {
 }
 static int dot3(const int32_t* a, const int32_t* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
+// the checks every view shares: the image's size and the cloud's (a row index must fit the low half of a z-buffer word)
+static int check_image(const char* who, int32_t H, int32_t W, int64_t n) {
+    PCC_REQUIRE(H >= 1 && H <= RENDER_MAX_DIM && W >= 1 && W <= RENDER_MAX_DIM, "%s: H and W must be 1 .. %d (got %d x %d)", who,
+                RENDER_MAX_DIM, H, W);
+    PCC_REQUIRE(n >= 0 && n <= 0xFFFFFFFEll, "%s: 0 .. 2^32 - 2 points", who);
+    return PCC_OK;
+}
+
 // the checks pcc_render_view and pcc_view_visibility share: the view's axes, the splat's sizes, the image's and the cloud's
 static int check_view(const char* who, const int32_t* right, const int32_t* up, const int32_t* front, int32_t scale, int32_t point_size,
                       int32_t H, int32_t W, int64_t n) {
@@ -356,9 +336,7 @@ static int check_view(const char* who, const int32_t* right, const int32_t* up, 
     PCC_REQUIRE(cross[0] == right[0] && cross[1] == right[1] && cross[2] == right[2], "%s: right must be up x front", who);
     PCC_REQUIRE(scale >= 1 && scale <= 64, "%s: scale must be 1 .. 64 (got %d)", who, scale);
     PCC_REQUIRE(point_size >= 1 && point_size <= 16, "%s: point_size must be 1 .. 16 (got %d)", who, point_size);
-    PCC_REQUIRE(H >= 1 && H <= RENDER_MAX_DIM && W >= 1 && W <= RENDER_MAX_DIM, "%s: H and W must be 1 .. %d (got %d x %d)", who,
-                RENDER_MAX_DIM, H, W);
-    PCC_REQUIRE(n >= 0 && n <= 0xFFFFFFFEll, "%s: 0 .. 2^32 - 2 points", who);
+    if (int rc = check_image(who, H, W, n)) return rc;
     return PCC_OK;
 }
 
@@ -387,9 +365,7 @@ static int check_camera(const char* who, const int32_t* pos_q, const int32_t* ax
     PCC_REQUIRE(focal_q >= 1 && focal_q <= CAMERA_FOCAL_MAX, "%s: focal_q must be 1 .. 2^20 (got %d)", who, focal_q);
     PCC_REQUIRE(near_q >= 1, "%s: near_q must be at least 1 (got %d)", who, near_q);
     PCC_REQUIRE(ps_q >= 1 && ps_q <= 256, "%s: ps_q must be 1 .. 256 (got %d)", who, ps_q);
-    PCC_REQUIRE(H >= 1 && H <= RENDER_MAX_DIM && W >= 1 && W <= RENDER_MAX_DIM, "%s: H and W must be 1 .. %d (got %d x %d)", who,
-                RENDER_MAX_DIM, H, W);
-    PCC_REQUIRE(n >= 0 && n <= 0xFFFFFFFEll, "%s: 0 .. 2^32 - 2 points", who);
+    if (int rc = check_image(who, H, W, n)) return rc;
     for (int r = 0; r < 3; ++r) {                         // |axis . e| <= sum |axis_k| (|pos_k| + 16 COORD_LIMIT), < 2^41 whatever the caller gave
         int64_t reach = 0;
         for (int k = 0; k < 3; ++k) {
@@ -411,6 +387,44 @@ static CameraView make_camera(const int32_t* pos_q, const int32_t* axes_q, int32
     return a;
 }
 
+// What the two render entries share, after the view's own checks: clear, splat, resolve.
+template <class View>
+static int draw(const char* who, const View& a, const int32_t* coords, const uint8_t* rgb8, int64_t n, const uint8_t* background,
+                void* scratch, int64_t scratch_bytes, uint8_t* image, void* stream) {
+    PCC_REQUIRE(background, "%s: background required", who);
+    PCC_REQUIRE(n == 0 || (coords && rgb8), "%s: null cloud with n > 0", who);
+    PCC_REQUIRE(scratch && image, "%s: z-buffer and image required", who);
+    PCC_REQUIRE(scratch_bytes >= pcc_render_scratch_bytes(a.H, a.W), "%s: scratch too small", who);
+    const int64_t npix = (int64_t)a.H * a.W;
+    const uint32_t bg = (uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16);
+    hipStream_t st = as_stream(stream);
+    uint64_t* zbuf = reinterpret_cast<uint64_t*>(scratch);
+    hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
+    if (n > 0) hipLaunchKernelGGL(splat_kernel<View>, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
+    hipLaunchKernelGGL(render_resolve_kernel, dim3(blocks_for((npix + 3) / 4, 256)), dim3(256), 0, st, zbuf, rgb8, bg, npix, image);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+// What the two visibility entries share: clear, splat, gather.  `depth` is an output only of a view that has one.
+template <class View>
+static int look_back(const char* who, const View& a, const int32_t* coords, int64_t n, void* scratch, int64_t scratch_bytes,
+                     int32_t accumulate, int32_t* behind, int32_t* won, int32_t* depth, void* stream) {
+    PCC_REQUIRE(n == 0 || (coords && behind && won && (depth || !View::HAS_DEPTH)), "%s: null cloud or outputs with n > 0", who);
+    PCC_REQUIRE(scratch, "%s: z-buffer required", who);
+    PCC_REQUIRE(scratch_bytes >= pcc_visibility_scratch_bytes(a.H, a.W), "%s: scratch too small", who);
+    if (n == 0) return PCC_OK;                                // nothing to write, and the z-buffer is scratch: nothing to launch
+    const int64_t npix = (int64_t)a.H * a.W;
+    hipStream_t st = as_stream(stream);
+    uint64_t* zbuf = reinterpret_cast<uint64_t*>(scratch);
+    hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
+    hipLaunchKernelGGL(splat_kernel<View>, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
+    hipLaunchKernelGGL(gather_kernel<View>, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf, accumulate != 0, behind, won,
+                       depth);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
 }  // namespace pcc
 
 using namespace pcc;
@@ -422,85 +436,38 @@ int64_t pcc_render_scratch_bytes(int32_t H, int32_t W) {
     return (int64_t)H * W * 8;
 }
 
+int64_t pcc_visibility_scratch_bytes(int32_t H, int32_t W) { return pcc_render_scratch_bytes(H, W); }
+
 int pcc_render_view(const int32_t* coords, const uint8_t* rgb8, int64_t n, const int32_t* right, const int32_t* up, const int32_t* front,
                     int32_t u_min, int32_t v_max, int32_t ox, int32_t oy, int32_t scale, int32_t point_size, int32_t H, int32_t W,
                     const uint8_t* background, void* scratch, int64_t scratch_bytes, uint8_t* image, void* stream) {
     if (int rc = check_view("pcc_render_view", right, up, front, scale, point_size, H, W, n)) return rc;
-    PCC_REQUIRE(background, "pcc_render_view: background required");
-    PCC_REQUIRE(n == 0 || (coords && rgb8), "pcc_render_view: null cloud with n > 0");
-    PCC_REQUIRE(scratch && image, "pcc_render_view: z-buffer and image required");
-    PCC_REQUIRE(scratch_bytes >= pcc_render_scratch_bytes(H, W), "pcc_render_view: scratch too small");
-    const RenderView a = make_view(right, up, front, u_min, v_max, ox, oy, scale, point_size, H, W);
-    const int64_t npix = (int64_t)H * W;
-    const uint32_t bg = (uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16);
-    hipStream_t st = as_stream(stream);
-    uint64_t* zbuf = reinterpret_cast<uint64_t*>(scratch);
-    hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
-    if (n > 0) hipLaunchKernelGGL(render_splat_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
-    hipLaunchKernelGGL(render_resolve_kernel, dim3(blocks_for((npix + 3) / 4, 256)), dim3(256), 0, st, zbuf, rgb8, bg, npix, image);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    return draw("pcc_render_view", make_view(right, up, front, u_min, v_max, ox, oy, scale, point_size, H, W), coords, rgb8, n, background,
+                scratch, scratch_bytes, image, stream);
 }
-
-int64_t pcc_visibility_scratch_bytes(int32_t H, int32_t W) { return pcc_render_scratch_bytes(H, W); }
 
 int pcc_view_visibility(const int32_t* coords, int64_t n, const int32_t* right, const int32_t* up, const int32_t* front, int32_t u_min,
                         int32_t v_max, int32_t ox, int32_t oy, int32_t scale, int32_t point_size, int32_t H, int32_t W, void* scratch,
                         int64_t scratch_bytes, int32_t accumulate, int32_t* behind, int32_t* won, void* stream) {
     if (int rc = check_view("pcc_view_visibility", right, up, front, scale, point_size, H, W, n)) return rc;
-    PCC_REQUIRE(n == 0 || (coords && behind && won), "pcc_view_visibility: null cloud or outputs with n > 0");
-    PCC_REQUIRE(scratch, "pcc_view_visibility: z-buffer required");
-    PCC_REQUIRE(scratch_bytes >= pcc_visibility_scratch_bytes(H, W), "pcc_view_visibility: scratch too small");
-    if (n == 0) return PCC_OK;                                // nothing to write, and the z-buffer is scratch: nothing to launch
-    const RenderView a = make_view(right, up, front, u_min, v_max, ox, oy, scale, point_size, H, W);
-    const int64_t npix = (int64_t)H * W;
-    hipStream_t st = as_stream(stream);
-    uint64_t* zbuf = reinterpret_cast<uint64_t*>(scratch);
-    hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
-    hipLaunchKernelGGL(render_splat_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
-    hipLaunchKernelGGL(visibility_gather_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf, accumulate != 0, behind, won);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    return look_back("pcc_view_visibility", make_view(right, up, front, u_min, v_max, ox, oy, scale, point_size, H, W), coords, n, scratch,
+                     scratch_bytes, accumulate, behind, won, nullptr, stream);
 }
 
 int pcc_render_camera(const int32_t* coords, const uint8_t* rgb8, int64_t n, const int32_t* pos_q, const int32_t* axes_q, int32_t focal_q,
                       int32_t near_q, int32_t H, int32_t W, int32_t ps_q, const uint8_t* background, void* scratch, int64_t scratch_bytes,
                       uint8_t* image, void* stream) {
     if (int rc = check_camera("pcc_render_camera", pos_q, axes_q, focal_q, near_q, ps_q, H, W, n)) return rc;
-    PCC_REQUIRE(background, "pcc_render_camera: background required");
-    PCC_REQUIRE(n == 0 || (coords && rgb8), "pcc_render_camera: null cloud with n > 0");
-    PCC_REQUIRE(scratch && image, "pcc_render_camera: z-buffer and image required");
-    PCC_REQUIRE(scratch_bytes >= pcc_render_scratch_bytes(H, W), "pcc_render_camera: scratch too small");
-    const CameraView a = make_camera(pos_q, axes_q, focal_q, near_q, ps_q, H, W);
-    const int64_t npix = (int64_t)H * W;
-    const uint32_t bg = (uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16);
-    hipStream_t st = as_stream(stream);
-    uint64_t* zbuf = reinterpret_cast<uint64_t*>(scratch);
-    hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
-    if (n > 0) hipLaunchKernelGGL(camera_splat_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
-    hipLaunchKernelGGL(render_resolve_kernel, dim3(blocks_for((npix + 3) / 4, 256)), dim3(256), 0, st, zbuf, rgb8, bg, npix, image);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    return draw("pcc_render_camera", make_camera(pos_q, axes_q, focal_q, near_q, ps_q, H, W), coords, rgb8, n, background, scratch,
+                scratch_bytes, image, stream);
 }
 
 int pcc_camera_visibility(const int32_t* coords, int64_t n, const int32_t* pos_q, const int32_t* axes_q, int32_t focal_q, int32_t near_q,
                           int32_t H, int32_t W, int32_t ps_q, void* scratch, int64_t scratch_bytes, int32_t accumulate, int32_t* behind,
                           int32_t* won, int32_t* depth, void* stream) {
     if (int rc = check_camera("pcc_camera_visibility", pos_q, axes_q, focal_q, near_q, ps_q, H, W, n)) return rc;
-    PCC_REQUIRE(n == 0 || (coords && behind && won && depth), "pcc_camera_visibility: null cloud or outputs with n > 0");
-    PCC_REQUIRE(scratch, "pcc_camera_visibility: z-buffer required");
-    PCC_REQUIRE(scratch_bytes >= pcc_render_scratch_bytes(H, W), "pcc_camera_visibility: scratch too small");
-    if (n == 0) return PCC_OK;                                // nothing to write, and the z-buffer is scratch: nothing to launch
-    const CameraView a = make_camera(pos_q, axes_q, focal_q, near_q, ps_q, H, W);
-    const int64_t npix = (int64_t)H * W;
-    hipStream_t st = as_stream(stream);
-    uint64_t* zbuf = reinterpret_cast<uint64_t*>(scratch);
-    hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
-    hipLaunchKernelGGL(camera_splat_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
-    hipLaunchKernelGGL(camera_gather_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf, accumulate != 0, behind, won,
-                       depth);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    return look_back("pcc_camera_visibility", make_camera(pos_q, axes_q, focal_q, near_q, ps_q, H, W), coords, n, scratch, scratch_bytes,
+                     accumulate, behind, won, depth, stream);
 }
 
 int32_t pcc_image_compare_tile(void) { return IC_TILE; }

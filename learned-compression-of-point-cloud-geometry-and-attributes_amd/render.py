@@ -117,17 +117,54 @@ def colours_to_bytes(rgb):
     return torch.clamp(torch.round(rgb.to(torch.float32) * 255.0), 0.0, 255.0).to(torch.uint8)
 
 
-def _sorted_coords(L, xyz, n, dev):
-    """(batch 0, x, y, z) rows on ``dev`` in canonical (x, y, z) order and the permutation that put them there (None for n < 2)"""
+def _cloud(who, cloud, device, colours=False):
+    """What every operator ``who`` checks first -> (cloud, xyz, n, dev): the cloud as a tensor, its integer xyz columns, its row
+    count and the GPU the call runs on (``device``, else the cloud's, else cuda:0)"""
+    cloud, xyz = _int_xyz(cloud)
+    if colours and cloud.shape[1] < 6:
+        raise ValueError("a cloud is a [N, 6] array: x, y, z, r, g, b")
+    dev = torch.device(device) if device is not None else (cloud.device if cloud.is_cuda else torch.device("cuda:0"))
+    if dev.type != "cuda":
+        raise ValueError("%s runs on the GPU: got device %s" % (who, dev))
+    n = int(cloud.shape[0])
+    if n and int(xyz.abs().max()) > COORD_LIMIT:
+        raise ValueError("%s: coordinates beyond +-%d" % (who, COORD_LIMIT))
+    return cloud, xyz, n, dev
+
+
+def _background(background):
+    bg = np.asarray(background)
+    if bg.shape != (3,) or bg.min() < 0 or bg.max() > 255:
+        raise ValueError("background is three bytes")
+    return bg.astype(np.uint8)
+
+
+def _sorted_rows(L, cloud, xyz, dev, colours):
+    """-> (coords, rgb8, perm): the (batch 0, x, y, z) int32 rows on ``dev`` in canonical (x, y, z) order — the tie rule's
+    "lowest row" —, the colours of ``cloud`` as bytes in that order (None unless ``colours``) and the permutation that put them
+    there (None for fewer than two rows)"""
+    n = int(xyz.shape[0])
     coords = torch.cat([torch.zeros((n, 1), dtype=torch.int32, device=dev), xyz.to(dev)], dim=1).contiguous()
+    rgb8 = colours_to_bytes(cloud[:, 3:6].to(dev)).contiguous() if colours else None
     if n < 2:
-        return coords, None
+        return coords, rgb8, None
     nbytes = L.pcc_sort_scratch_bytes(n)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     perm = torch.empty(n, dtype=torch.int32, device=dev)
     check(L.pcc_sort_coords(ptr(coords), n, ptr(perm), ptr(scratch), nbytes, _lib.stream()))
     perm = perm.long()
-    return coords[perm].contiguous(), perm
+    return coords[perm].contiguous(), rgb8[perm].contiguous() if colours else None, perm
+
+
+def _zbuffer(L, dev, sizes):
+    """-> (zbuf, zbytes): one z-buffer on ``dev`` large enough for every (H, W) of ``sizes`` (0 bytes for a size the entries refuse)"""
+    zbytes = max(L.pcc_render_scratch_bytes(H, W) for H, W in sizes)
+    return torch.empty(max(zbytes, 8), dtype=torch.uint8, device=dev), zbytes
+
+
+def _input_order(perm, *outs):
+    """per-row outputs of canonically sorted rows -> the same in the input's row order"""
+    return outs if perm is None else tuple(torch.empty_like(t).index_copy_(0, perm, t) for t in outs)
 
 
 def render_view(cloud, front, up, H, W, frame=None, point_size=None, background=(255, 255, 255), device=None):
@@ -137,37 +174,22 @@ def render_view(cloud, front, up, H, W, frame=None, point_size=None, background=
     ``frame``: a ``view_frame`` result (of this or of another cloud — reconstructions are rendered in their source's
     frame); None frames the cloud itself.  ``point_size=None`` means the frame's scale: adjacent voxels tile the image
     without gaps or overlap."""
-    L = _lib.lib()
     r, u, f = view_axes(front, up)
-    cloud, xyz = _int_xyz(cloud)
-    if cloud.shape[1] < 6:
-        raise ValueError("a cloud is a [N, 6] array: x, y, z, r, g, b")
-    dev = torch.device(device) if device is not None else (cloud.device if cloud.is_cuda else torch.device("cuda:0"))
-    if dev.type != "cuda":
-        raise ValueError("render_view runs on the GPU: got device %s" % dev)
-    n = int(cloud.shape[0])
-    if n and int(xyz.abs().max()) > COORD_LIMIT:
-        raise ValueError("render_view: coordinates beyond +-%d" % COORD_LIMIT)
+    cloud, xyz, n, dev = _cloud("render_view", cloud, device, colours=True)
     if frame is None:
         frame = view_frame(xyz, f, u, H, W)
     u_min, _, _, v_max, scale, ox, oy = (int(v) for v in frame)
     point_size = scale if point_size is None else int(point_size)
-    bg = np.asarray(background)
-    if bg.shape != (3,) or bg.min() < 0 or bg.max() > 255:
-        raise ValueError("background is three bytes")
-    bg = bg.astype(np.uint8)
+    bg = _background(background)
+    H, W = int(H), int(W)
+    L = _lib.lib()
     with torch.cuda.device(dev):
-        coords, perm = _sorted_coords(L, xyz, n, dev)  # canonical (x, y, z) order: the tie rule's "lowest row"
-        rgb8 = colours_to_bytes(cloud[:, 3:6].to(dev)).contiguous()
-        if perm is not None:
-            rgb8 = rgb8[perm].contiguous()
-        zbytes = L.pcc_render_scratch_bytes(int(H), int(W))
-        zbuf = torch.empty(max(zbytes, 8), dtype=torch.uint8, device=dev)
-        image = torch.empty((int(H), int(W), 3), dtype=torch.uint8, device=dev) if zbytes else None
+        coords, rgb8, _ = _sorted_rows(L, cloud, xyz, dev, colours=True)
+        zbuf, zbytes = _zbuffer(L, dev, [(H, W)])
+        image = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if zbytes else None
         axes = [np.asarray(a, dtype=np.int32) for a in (r, u, f)]
         check(L.pcc_render_view(ptr(coords) if n else None, ptr(rgb8) if n else None, n, ptr(axes[0]), ptr(axes[1]), ptr(axes[2]),
-                                u_min, v_max, ox, oy, scale, point_size, int(H), int(W), ptr(bg), ptr(zbuf), zbytes, ptr(image),
-                                _lib.stream()))
+                                u_min, v_max, ox, oy, scale, point_size, H, W, ptr(bg), ptr(zbuf), zbytes, ptr(image), _lib.stream()))
     return image
 
 
@@ -203,7 +225,6 @@ def visibility(cloud, views, H, W, frames=None, point_size=None, device=None):
     ``VIEWS`` or (front, up) pairs.  ``frames``: None (every view frames the cloud itself at H x W) or one ``view_frame`` result
     per view (a reconstruction is analysed in its source's frames).  ``point_size=None`` means each frame's scale.  Not a
     camera: orthographic, axis views only, square splats."""
-    cloud, xyz = _int_xyz(cloud)
     axes = _views(views)
     if frames is not None:
         if not isinstance(frames, (list, tuple)) or len(frames) != len(axes):
@@ -213,22 +234,15 @@ def visibility(cloud, views, H, W, frames=None, point_size=None, device=None):
     H, W = int(H), int(W)
     if not (1 <= H <= MAX_DIM and 1 <= W <= MAX_DIM):
         raise ValueError("H and W must be 1 .. %d (got %d x %d)" % (MAX_DIM, H, W))
-    dev = torch.device(device) if device is not None else (cloud.device if cloud.is_cuda else torch.device("cuda:0"))
-    if dev.type != "cuda":
-        raise ValueError("visibility runs on the GPU: got device %s" % dev)
-    n = int(cloud.shape[0])
-    if n and int(xyz.abs().max()) > COORD_LIMIT:
-        raise ValueError("visibility: coordinates beyond +-%d" % COORD_LIMIT)
+    cloud, xyz, n, dev = _cloud("visibility", cloud, device)
     L = _lib.lib()
     with torch.cuda.device(dev):
-        xyz = xyz.to(dev)
-        coords, perm = _sorted_coords(L, xyz, n, dev)  # canonical (x, y, z) order: the tie rule's "lowest row"
-        zbytes = L.pcc_visibility_scratch_bytes(H, W)
-        zbuf = torch.empty(max(zbytes, 8), dtype=torch.uint8, device=dev)
-        behind = torch.empty(n, dtype=torch.int32, device=dev)
-        won = torch.empty(n, dtype=torch.int32, device=dev)
+        behind, won = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
         if n == 0:                                     # nothing to frame and nothing to ask
             return behind, won
+        xyz = xyz.to(dev)
+        coords, _, perm = _sorted_rows(L, cloud, xyz, dev, colours=False)
+        zbuf, zbytes = _zbuffer(L, dev, [(H, W)])
         for k, (r, u, f) in enumerate(axes):
             frame = view_frame(xyz, f, u, H, W) if frames is None else frames[k]
             u_min, _, _, v_max, scale, ox, oy = (int(v) for v in frame)
@@ -236,9 +250,7 @@ def visibility(cloud, views, H, W, frames=None, point_size=None, device=None):
             vecs = [np.asarray(a, dtype=np.int32) for a in (r, u, f)]
             check(L.pcc_view_visibility(ptr(coords), n, ptr(vecs[0]), ptr(vecs[1]), ptr(vecs[2]), u_min, v_max, ox, oy, scale, size, H, W,
                                         ptr(zbuf), zbytes, int(k > 0), ptr(behind), ptr(won), _lib.stream()))
-        if perm is not None:                           # back to the input's row order
-            behind, won = torch.empty_like(behind).index_copy_(0, perm, behind), torch.empty_like(won).index_copy_(0, perm, won)
-    return behind, won
+        return _input_order(perm, behind, won)
 
 
 CameraInts = collections.namedtuple("CameraInts", "pos_q axes_q focal_q near_q H W")
@@ -382,28 +394,13 @@ def render_camera(cloud, camera, point_size=1.0, background=(255, 255, 255), dev
     if not isinstance(camera, Camera):
         raise ValueError("render_camera: camera is a render.Camera, got %r" % (camera,))
     ps_q = _ps_q(point_size)
-    cloud, xyz = _int_xyz(cloud)
-    if cloud.shape[1] < 6:
-        raise ValueError("a cloud is a [N, 6] array: x, y, z, r, g, b")
-    dev = torch.device(device) if device is not None else (cloud.device if cloud.is_cuda else torch.device("cuda:0"))
-    if dev.type != "cuda":
-        raise ValueError("render_camera runs on the GPU: got device %s" % dev)
-    n = int(cloud.shape[0])
-    if n and int(xyz.abs().max()) > COORD_LIMIT:
-        raise ValueError("render_camera: coordinates beyond +-%d" % COORD_LIMIT)
-    bg = np.asarray(background)
-    if bg.shape != (3,) or bg.min() < 0 or bg.max() > 255:
-        raise ValueError("background is three bytes")
-    bg = bg.astype(np.uint8)
+    cloud, xyz, n, dev = _cloud("render_camera", cloud, device, colours=True)
+    bg = _background(background)
     pos, axes, q = _camera_args(camera)
     L = _lib.lib()
     with torch.cuda.device(dev):
-        coords, perm = _sorted_coords(L, xyz, n, dev)
-        rgb8 = colours_to_bytes(cloud[:, 3:6].to(dev)).contiguous()
-        if perm is not None:
-            rgb8 = rgb8[perm].contiguous()
-        zbytes = L.pcc_render_scratch_bytes(q.H, q.W)
-        zbuf = torch.empty(max(zbytes, 8), dtype=torch.uint8, device=dev)
+        coords, rgb8, _ = _sorted_rows(L, cloud, xyz, dev, colours=True)
+        zbuf, zbytes = _zbuffer(L, dev, [(q.H, q.W)])
         image = torch.empty((q.H, q.W, 3), dtype=torch.uint8, device=dev)
         check(L.pcc_render_camera(ptr(coords) if n else None, ptr(rgb8) if n else None, n, ptr(pos), ptr(axes), q.focal_q, q.near_q,
                                   q.H, q.W, ps_q, ptr(bg), ptr(zbuf), zbytes, ptr(image), _lib.stream()))
@@ -428,28 +425,19 @@ def camera_visibility(cloud, cameras, point_size=1.0, device=None):
     if any(not isinstance(c, Camera) for c in cameras):
         raise ValueError("cameras is a list of render.Camera, got %r" % (cameras,))
     ps_q = _ps_q(point_size)
-    cloud, xyz = _int_xyz(cloud)
-    dev = torch.device(device) if device is not None else (cloud.device if cloud.is_cuda else torch.device("cuda:0"))
-    if dev.type != "cuda":
-        raise ValueError("camera_visibility runs on the GPU: got device %s" % dev)
-    n = int(cloud.shape[0])
-    if n and int(xyz.abs().max()) > COORD_LIMIT:
-        raise ValueError("camera_visibility: coordinates beyond +-%d" % COORD_LIMIT)
+    cloud, xyz, n, dev = _cloud("camera_visibility", cloud, device)
     L = _lib.lib()
     with torch.cuda.device(dev):
         behind, won, depth = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
         if n == 0:
             return behind, won, depth
-        coords, perm = _sorted_coords(L, xyz, n, dev)
-        zbytes = max(L.pcc_render_scratch_bytes(c.H, c.W) for c in cameras)
-        zbuf = torch.empty(max(zbytes, 8), dtype=torch.uint8, device=dev)
+        coords, _, perm = _sorted_rows(L, cloud, xyz, dev, colours=False)
+        zbuf, zbytes = _zbuffer(L, dev, [(c.H, c.W) for c in cameras])
         for k, camera in enumerate(cameras):
             pos, axes, q = _camera_args(camera)
             check(L.pcc_camera_visibility(ptr(coords), n, ptr(pos), ptr(axes), q.focal_q, q.near_q, q.H, q.W, ps_q, ptr(zbuf), zbytes,
                                           int(k > 0), ptr(behind), ptr(won), ptr(depth), _lib.stream()))
-        if perm is not None:                           # back to the input's row order
-            behind, won, depth = (torch.empty_like(t).index_copy_(0, perm, t) for t in (behind, won, depth))
-    return behind, won, depth
+        return _input_order(perm, behind, won, depth)
 
 
 def data_range_of(ref_min):

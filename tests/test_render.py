@@ -167,3 +167,47 @@ def test_coordinates_at_the_limit(pcc, shift):
     beyond[0, 0] = 130001 if shift[0] > 0 else -130001
     with pytest.raises(ValueError):
         render.render_view(torch.from_numpy(beyond).to(DEV), FRONT[0], FRONT[1], 8, 8)
+
+
+def c_entry(pcc, rows, rgb, view, frame, point_size, H, W, background=(255, 255, 255)):
+    """pcc_render_view itself on rows (batch, x, y, z) and byte colours AS GIVEN (no sort) -> (rc, image); the image holds
+    the bytes 7 before the call"""
+    from pcc_amd import _lib
+    L = pcc.lib()
+    rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 4)
+    n = rows.shape[0]
+    vecs = [np.ascontiguousarray(a, dtype=np.int32) for a in ref.axes(view[0], view[1])]
+    coords, rgb8 = torch.from_numpy(rows).to(DEV), torch.from_numpy(np.ascontiguousarray(rgb, dtype=np.uint8)).to(DEV)
+    bg = np.asarray(background, dtype=np.uint8)
+    nbytes = int(L.pcc_render_scratch_bytes(H, W))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    image = torch.full((H, W, 3), 7, dtype=torch.uint8, device=DEV)
+    u_min, _, _, v_max, scale, ox, oy = frame
+    torch.cuda.synchronize()
+    rc = L.pcc_render_view(coords.data_ptr(), rgb8.data_ptr(), n, vecs[0].ctypes.data, vecs[1].ctypes.data, vecs[2].ctypes.data, u_min, v_max,
+                           ox, oy, scale, point_size, H, W, bg.ctypes.data, scratch.data_ptr(), nbytes, image.data_ptr(), _lib.stream())
+    torch.cuda.synchronize()
+    return rc, image.cpu().numpy()
+
+
+def test_frames_anywhere_in_int32(pcc):
+    """u_min, v_max, ox and oy are the caller's and may be anywhere in int32: the pixel positions are worked out and clipped in
+    64 bits before they are narrowed.  Five points at scale 64 with squares of 16 in a 72 x 72 image, through the entry."""
+    xyz = np.array([(0, 0, 0), (0, 0, 2), (1, 0, 0), (0, 1, 2), (1, 1, -3)], dtype=np.int64)
+    rgb = np.array([(250, 0, 0), (0, 250, 0), (0, 0, 250), (250, 250, 0), (0, 250, 250)], dtype=np.uint8)
+    rows = np.concatenate([np.zeros((5, 1), dtype=np.int64), xyz], axis=1)
+    H = W = 72
+    # the intermediates (u + 2^25) 64 and (2^25 + 1 - v) 64 are about 2^31 and cancel against ox, oy: columns 64 u, rows 64 (1 - v)
+    frame = (-2 ** 25, 0, 0, 2 ** 25 + 1, 64, -2 ** 31, -2 ** 31)
+    want = ref.render(xyz, rgb, FRONT[0], FRONT[1], H, W, frame, point_size=16, background=(1, 2, 3))
+    rc, got = c_entry(pcc, rows, rgb, FRONT, frame, 16, H, W, background=(1, 2, 3))
+    assert rc == 0 and np.array_equal(got, want), "%d pixels differ" % int((got != want).any(axis=2).sum())
+    # by hand: (0, 1, 2) whole at the top left, (1, 1, -3) cut to 8 columns, (0, 0, 2) over (0, 0, 0) cut to 8 rows, (1, 0, 0) to 8 x 8
+    assert (got[0:16, 0:16] == rgb[3]).all() and (got[0:16, 64:72] == rgb[4]).all()
+    assert (got[64:72, 0:16] == rgb[1]).all() and (got[64:72, 64:72] == rgb[2]).all()
+    assert int((got != np.array([1, 2, 3], dtype=np.uint8)).any(axis=2).sum()) == 256 + 128 + 128 + 64
+    # the corners of int32: every row is far off-screen, and nothing wraps round
+    for frame in ((2 ** 31 - 1, 0, 0, -2 ** 31, 64, 2 ** 31 - 1, -2 ** 31), (-2 ** 31, 0, 0, 2 ** 31 - 1, 64, -2 ** 31, 2 ** 31 - 1)):
+        want = ref.render(xyz, rgb, FRONT[0], FRONT[1], H, W, frame, point_size=16)
+        rc, got = c_entry(pcc, rows, rgb, FRONT, frame, 16, H, W)
+        assert rc == 0 and np.array_equal(got, want) and (got == 255).all()

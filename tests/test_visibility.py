@@ -130,6 +130,27 @@ def test_clipping_at_each_edge_and_off_screen(pcc):
         assert (b == ref.OFFSCREEN).all() and (w == 0).all()
 
 
+def test_frames_anywhere_in_int32(pcc):
+    """u_min, v_max, ox and oy are the caller's and may be anywhere in int32: the pixel positions are worked out and clipped in
+    64 bits before they are narrowed.  Five points at scale 64 with squares of 16 in a 72 x 72 image, through the entry."""
+    xyz = np.array([(0, 0, 0), (0, 0, 2), (1, 0, 0), (0, 1, 2), (1, 1, -3)], dtype=np.int64)
+    rows = np.concatenate([np.zeros((5, 1), dtype=np.int64), xyz], axis=1)
+    H = W = 72
+    # the intermediates (u + 2^25) 64 and (2^25 + 1 - v) 64 are about 2^31 and cancel against ox, oy: columns 64 u, rows 64 (1 - v)
+    frame = (-2 ** 25, 0, 0, 2 ** 25 + 1, 64, -2 ** 31, -2 ** 31)
+    want_b, want_w = ref.view_visibility(xyz, FRONT[0], FRONT[1], H, W, frame, point_size=16)
+    rc, b, w = c_entry(pcc, rows, FRONT, frame, 16, H, W, fill=(-7, -7))
+    assert rc == 0 and np.array_equal(b, want_b) and np.array_equal(w, want_w)
+    # by hand: every splat lands; (0, 0, 0) lies 2 behind (0, 0, 2); the right column and the bottom row of splats are cut to 8
+    assert b.tolist() == [2, 0, 0, 0, 0] and w.tolist() == [0, 16 * 8, 8 * 8, 16 * 16, 8 * 16]
+    # the corners of int32: every row is far off-screen, and nothing wraps round
+    for frame in ((2 ** 31 - 1, 0, 0, -2 ** 31, 64, 2 ** 31 - 1, -2 ** 31), (-2 ** 31, 0, 0, 2 ** 31 - 1, 64, -2 ** 31, 2 ** 31 - 1)):
+        want_b, want_w = ref.view_visibility(xyz, FRONT[0], FRONT[1], H, W, frame, point_size=16)
+        rc, b, w = c_entry(pcc, rows, FRONT, frame, 16, H, W, fill=(-7, -7))
+        assert rc == 0 and np.array_equal(b, want_b) and np.array_equal(w, want_w)
+        assert (b == ref.OFFSCREEN).all() and (w == 0).all()
+
+
 def test_depth_range(pcc):
     two = np.array([[0, 0, -LIMIT], [0, 0, LIMIT]], dtype=np.int64)
     b, w = check(two, [FRONT], 1, 1)

@@ -82,12 +82,7 @@ def main():
 
     # rows sorted once for the entries
     L = _lib.lib()
-    coords = torch.cat([torch.zeros((n, 1), dtype=torch.int32, device=dev), cloud[:, :3].to(torch.int32)], dim=1).contiguous()
-    nbytes = L.pcc_sort_scratch_bytes(n)
-    scratch, perm = torch.empty(nbytes, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
-    check(L.pcc_sort_coords(ptr(coords), n, ptr(perm), ptr(scratch), nbytes, _lib.stream()))
-    coords = coords[perm.long()].contiguous()
-    rgb8 = render.colours_to_bytes(cloud[:, 3:6])[perm.long()].contiguous()
+    coords, rgb8, _ = render._sorted_rows(L, cloud, cloud[:, :3].to(torch.int32), dev, colours=True)
     behind, won, depth = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
     bg = np.full(3, 255, dtype=np.uint8)
     xyz = pts[:, :3].astype(np.int64)

@@ -71,12 +71,7 @@ def main():
 
     # the entries alone: rows sorted once, the frames known, every buffer allocated
     L = _lib.lib()
-    coords = torch.cat([torch.zeros((n, 1), dtype=torch.int32, device=dev), cloud[:, :3].to(torch.int32)], dim=1).contiguous()
-    nbytes = L.pcc_sort_scratch_bytes(n)
-    scratch, perm = torch.empty(nbytes, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
-    check(L.pcc_sort_coords(ptr(coords), n, ptr(perm), ptr(scratch), nbytes, _lib.stream()))
-    coords = coords[perm.long()].contiguous()
-    rgb8 = render.colours_to_bytes(cloud[:, 3:6])[perm.long()].contiguous()
+    coords, rgb8, _ = render._sorted_rows(L, cloud, cloud[:, :3].to(torch.int32), dev, colours=True)
     zbytes = L.pcc_visibility_scratch_bytes(H, W)
     zbuf = torch.empty(zbytes, dtype=torch.uint8, device=dev)
     image = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
