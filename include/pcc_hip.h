@@ -866,6 +866,55 @@ int pcc_raht_transform(double* values, int64_t n, int32_t c, const int32_t* left
                        const int32_t* w1, const int32_t* step_rows, const int32_t* step_offsets_host,
                        int32_t depth, int32_t inverse, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Region-wise quantisation of the RAHT coefficients (the "PCR2" stream of raht.py; DESIGN.md
+ * "Anchor codec: region-wise quantisation").  csrc/raht.hip.
+ *
+ * A quantisation LEVEL is an integer 0 .. 63; level l quantises with the step steps[l] of a
+ * 64-entry table the caller supplies (raht.py: level_steps, one Gaussian-table spacing per level).
+ * Blocks: the rows inside one cube of edge 2^block_log2 of the plan's grid.  In Morton row order
+ * they are runs of rows, and row i opens a block iff i = 0 or step[i] >= 3*block_log2: the
+ * plan alone gives the boundaries, no keys are needed.  A block's level is the MINIMUM (the
+ * finest) of its points' levels.  The coefficient of row i > 0 summarises the rows
+ * [left[i], i + w1[i]) and takes the minimum level among them; that range minimum equals a walk
+ * over the transform's steps, finest first, on lev[] = the block level of every row:
+ *     m = min(lev[left[i]], lev[i]);  coeff_level[i] = m;  lev[left[i]] = m
+ * Row 0 (the DC) takes lev[0] after the last step, the minimum over the cloud.  Every
+ * coefficient above a block of the finest level therefore carries that level, and the rows of
+ * such a block decode exactly as under uniform coding at it.  All of it is integer min: the
+ * results do not depend on any order of execution.
+ * ------------------------------------------------------------------------------------- */
+/* step: the plan's (DEVICE, n rows); 0 <= block_log2 <= 17 (block_log2 >= depth: one block).
+ * Outputs (DEVICE): block_of_row[n] int32, ascending from 0, and n_blocks[1] int32.
+ * scratch: pcc_raht_scratch_bytes(n).  Five launches (flags, three scan kernels, count). */
+int pcc_raht_blocks(const int32_t* step, int64_t n, int32_t block_log2, int32_t* block_of_row,
+                    int32_t* n_blocks, void* scratch, int64_t scratch_bytes, void* stream);
+/* levels: uint8 [n] per point in the INPUT row order (row i of the plan reads levels[perm[i]]),
+ * each 0 .. 63 -> block_level[n_blocks] int32 = the minimum over the block's rows (initialised
+ * here).  A segmented min over each wave, then one integer atomicMin per (wave, block).
+ * status[0] (int32, cleared here) counts the levels above 63; they are read as 63. */
+int pcc_raht_block_levels(const uint8_t* levels, const int32_t* perm, const int32_t* block_of_row,
+                          int64_t n, int64_t n_blocks, int32_t* block_level, int32_t* status,
+                          void* stream);
+/* block_level [n_blocks] int32 (values outside 0 .. 63 are clamped) -> coeff_level[n] uint8 by
+ * the walk above, on the launch plan of pcc_raht_transform: one launch per non-empty step, the
+ * top steps of at most 256 rows each in one workgroup, which also writes the DC's level.  No
+ * atomics.  lev: int32 [n] of scratch (the walk's working array).  step_offsets_host as for
+ * pcc_raht_transform, checked the same way. */
+int pcc_raht_coeff_levels(const int32_t* block_level, const int32_t* block_of_row, int64_t n,
+                          int64_t n_blocks, const int32_t* left, const int32_t* step_rows,
+                          const int32_t* step_offsets_host, int32_t depth, uint8_t* coeff_level,
+                          int32_t* lev, void* stream);
+/* coeffs [n,c] float64 -> symbols [n,c] int32 = rint(coeff / steps[coeff_level[row]]), ties to
+ * even, the division correctly rounded.  steps_host: a HOST float64[64], every entry positive
+ * and finite.  status[0] (cleared here) counts the symbols of magnitude >= 2^28 (or NaN); they
+ * are written as 0. */
+int pcc_raht_quantize(const double* coeffs, int64_t n, int32_t c, const uint8_t* coeff_level,
+                      const double* steps_host, int32_t* symbols, int32_t* status, void* stream);
+/* coeffs [n,c] float64 = symbol * steps[coeff_level[row]] (one rounding). */
+int pcc_raht_dequantize(const int32_t* symbols, int64_t n, int32_t c, const uint8_t* coeff_level,
+                        const double* steps_host, double* coeffs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

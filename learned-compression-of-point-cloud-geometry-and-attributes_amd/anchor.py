@@ -6,7 +6,11 @@ Geometry: lossless, the "PCO1" octree stream (octree.py), or with ``contexts=Tru
 (voxelize.downsample).  Attributes: RAHT coefficients quantised with one step size and range coded, "PCR1" (raht.py), by default
 in BT.709 YUV.  The RAHT plan uses the origin and depth of the PCO1 header, so the decoder rebuilds it from the geometry alone.
 
-Stream (little-endian):  "PCA1" | u8 colorspace (0 rgb, 1 yuv) | u8[3] 0 | u32 len_geometry | PCO1 | PCR1
+With a quality map (``compress(..., quality=...)``) the attributes are quantised region by region, "PCR2" (raht.py): the anchor's
+counterpart of G-PCC's region-wise QP offsets, so that the learned codec's spatially steered rows have a conventional baseline;
+``compress_to_bytes`` searches the qstep that meets a byte budget.
+
+Stream (little-endian):  "PCA1" | u8 colorspace (0 rgb, 1 yuv) | u8[3] 0 | u32 len_geometry | PCO1 or PCO2 | PCR1 or PCR2
 """
 import struct
 
@@ -53,10 +57,18 @@ def _geometry_header(pco1):
     return depth, (ox, oy, oz), n
 
 
-def compress(x, qstep, colorspace="yuv", path=None, contexts=False):
-    """x: [N,6] on the GPU (integer voxel coordinates as floats + rgb in [0, 1]; no voxel twice), ``qstep``: the quantisation
-    step of the RAHT coefficients (colour units: 1/255 is one 8-bit level) -> PCA1 bytes, also written to ``path`` if given.
-    ``contexts``: code the geometry as PCO2 (neighbour contexts) instead of PCO1; ``decompress`` reads either."""
+def _attribute_quality(quality, n, device):
+    """a quality map [N], [N,1] or [N,2] (a Q map's channels [q_g, q_a]: the attribute column counts) -> float64 [N] on
+    ``device``"""
+    q = quality if isinstance(quality, torch.Tensor) else torch.as_tensor(np.asarray(quality))
+    if q.dim() not in (1, 2) or q.shape[0] != n or (q.dim() == 2 and q.shape[1] not in (1, 2)):
+        raise ValueError(f"anchor: a quality map of shape {tuple(q.shape)}: need [{n}], [{n}, 1] or [{n}, 2]")
+    return q.reshape(n, -1)[:, -1].to(device=device, dtype=torch.float64)
+
+
+def _prepare(x, colorspace, contexts, quality, block_log2, span):
+    """what ``compress`` codes and does not depend on qstep: (the head of the stream with the geometry, the RAHT plan, the
+    coefficients, the ``raht.Region`` of the quality map or None)"""
     if colorspace not in COLORSPACES:
         raise ValueError(f"colorspace {colorspace!r}: 'yuv' or 'rgb'")
     if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
@@ -68,12 +80,66 @@ def compress(x, qstep, colorspace="yuv", path=None, contexts=False):
     geometry = octree.encode_coordinates(coords, 1, contexts=contexts)
     depth, origin, _ = _geometry_header(geometry)
     p = raht.plan(coords, origin=origin, depth=depth)
-    attributes = raht.encode_attributes(p, to_coded(x[:, 3:6], colorspace), qstep)
-    data = MAGIC + struct.pack("<B3xI", COLORSPACES[colorspace], len(geometry)) + geometry + attributes
+    region = None
+    if quality is not None:
+        region = raht.region(p, raht.quality_levels(_attribute_quality(quality, p.n, x.device), span), block_log2)
+    head = MAGIC + struct.pack("<B3xI", COLORSPACES[colorspace], len(geometry)) + geometry
+    return head, p, raht.forward(p, to_coded(x[:, 3:6], colorspace)), region
+
+
+def _code(p, coeffs, qstep, region):
+    """the attribute stream of the coefficients at ``qstep``: PCR1, or PCR2 with a region"""
+    return raht.encode_coefficients(p, coeffs, qstep) if region is None else raht.encode_region(p, coeffs, qstep, region)
+
+
+def compress(x, qstep, colorspace="yuv", path=None, contexts=False, quality=None, block_log2=3, span=24):
+    """x: [N,6] on the GPU (integer voxel coordinates as floats + rgb in [0, 1]; no voxel twice), ``qstep``: the quantisation
+    step of the RAHT coefficients (colour units: 1/255 is one 8-bit level) -> PCA1 bytes, also written to ``path`` if given.
+    ``contexts``: code the geometry as PCO2 (neighbour contexts) instead of PCO1; ``decompress`` reads either.
+
+    ``quality``: a quality map in x's row order, [N], [N,1] or [N,2] with values in [0, 1]; of two columns (a Q map's
+    [q_g, q_a]) the second, the attribute quality, is used: the geometry is lossless here, so a geometry quality has no
+    meaning.  The attributes are then the region-wise stream PCR2: every cube of edge 2^block_log2 is quantised with the
+    level ``raht.quality_levels(quality, span)`` of its best point, quality 1 at ``qstep`` itself, quality 0 at
+    ``raht.level_steps(qstep)[span]``.  The PCA1 container is the same; ``decompress`` tells the two by the attribute magic."""
+    head, p, coeffs, region = _prepare(x, colorspace, contexts, quality, block_log2, span)
+    data = head + _code(p, coeffs, qstep, region)
     if path is not None:
         with open(path, "wb") as f:
             f.write(data)
     return data
+
+
+def compress_to_bytes(x, target_bytes, quality=None, qstep_lo=0.25 / 255, qstep_hi=64 / 255, iterations=12, **kw):
+    """``compress`` at the finest qstep in [qstep_lo, qstep_hi] whose whole PCA1 stream has at most ``target_bytes`` bytes ->
+    (data, qstep, reached).  Bisection in log qstep, ``iterations`` probes after the two ends; geometry, plan, coefficients
+    and coefficient levels are made once, only the quantiser and the coder run per probe.  ``reached`` is False, with the
+    stream at ``qstep_hi``, when even that is larger than the target.  ``kw``: ``compress``'s colorspace, contexts,
+    block_log2, span."""
+    unknown = set(kw) - {"colorspace", "contexts", "block_log2", "span"}
+    if unknown:
+        raise ValueError("compress_to_bytes: unknown arguments %s" % sorted(unknown))
+    lo, hi = raht._check_qstep(qstep_lo), raht._check_qstep(qstep_hi)
+    if lo > hi:
+        raise ValueError(f"compress_to_bytes: qstep_lo {lo} above qstep_hi {hi}")
+    head, p, coeffs, region = _prepare(x, kw.get("colorspace", "yuv"), kw.get("contexts", False), quality, kw.get("block_log2", 3),
+                                       kw.get("span", 24))
+    probe = lambda q: head + _code(p, coeffs, q, region)
+    best = probe(hi)
+    if len(best) > target_bytes:
+        return best, hi, False
+    data = probe(lo)
+    if len(data) <= target_bytes:
+        return data, lo, True
+    best_q = hi
+    for _ in range(int(iterations)):
+        mid = float(np.sqrt(lo * hi))
+        data = probe(mid)
+        if len(data) <= target_bytes:
+            best, best_q, hi = data, mid, mid
+        else:
+            lo = mid
+    return best, best_q, True
 
 
 def decompress(data_or_path, device="cuda:0"):

@@ -1,6 +1,7 @@
 // RAHT, the region-adaptive hierarchical transform (de Queiroz & Chou 2016) of per-voxel attributes: the transform of G-PCC's
 // attribute coder, here the attribute half of the octree + RAHT anchor codec (../raht.py, ../anchor.py).  The contract is in
-// include/pcc_hip.h (pcc_raht_plan / pcc_raht_transform).
+// include/pcc_hip.h (pcc_raht_plan / pcc_raht_transform, and for region-wise quantisation pcc_raht_blocks / pcc_raht_block_levels /
+// pcc_raht_coeff_levels / pcc_raht_quantize / pcc_raht_dequantize).
 //
 // Rows are the voxels in ascending Morton order (the child index (x << 2) | (y << 1) | z of octree.hip at every level, so
 // pcc_octree_expand's output is already in row order).  The transform has 3 * depth steps, one per key bit, finest first; at
@@ -160,6 +161,138 @@ struct RahtScratch {
     }
 };
 
+// ---- region-wise quantisation ("PCR2", ../raht.py): blocks of rows, one quantisation level per block, one per coefficient -------
+// A block is the run of rows inside one cube of edge 2^block_log2: in Morton order a row opens a block iff its key differs from
+// the row before it at or above bit 3 * block_log2, which is what step[i] >= 3 * block_log2 says.  The plan is all that is needed.
+constexpr int RAHT_LEVELS = 64;               // quantisation levels 0 .. 63, one per Gaussian table spacing (raht.py: level_steps)
+
+__global__ __launch_bounds__(RAHT_BLOCK) void raht_block_flags_kernel(const int32_t* __restrict__ step, int64_t n, int first_step,
+                                                                      int32_t* __restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * RAHT_BLOCK + threadIdx.x;
+    if (i < n) flags[i] = (i > 0 && step[i] >= first_step) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(64) void raht_block_count_kernel(const int32_t* __restrict__ block_of_row, int64_t n, int32_t* __restrict__ n_blocks) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) n_blocks[0] = block_of_row[n - 1] + 1;
+}
+
+__global__ __launch_bounds__(RAHT_BLOCK) void raht_fill_kernel(int32_t* __restrict__ out, int64_t m, int32_t value) {
+    const int64_t i = (int64_t)blockIdx.x * RAHT_BLOCK + threadIdx.x;
+    if (i < m) out[i] = value;
+}
+
+// block_level[b] = min over the block's rows of levels[perm[row]].  Rows of one block are consecutive, so inside a wave the lanes
+// of a block form a segment: a segmented min scan over the wave (six shuffle rounds), then the last lane of every segment sends
+// one atomicMin.  Integer min only: the result does not depend on the order in which the waves arrive.
+__global__ __launch_bounds__(RAHT_BLOCK) void raht_block_levels_kernel(const uint8_t* __restrict__ levels, const int32_t* __restrict__ perm,
+                                                                       const int32_t* __restrict__ block_of_row, int64_t n, int64_t n_blocks,
+                                                                       int32_t* __restrict__ block_level, int32_t* __restrict__ status) {
+    const int64_t i = (int64_t)blockIdx.x * RAHT_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int blk = -1, lvl = RAHT_LEVELS - 1;
+    if (i < n) {
+        const int64_t src = perm[i];
+        const int64_t b = block_of_row[i];
+        if ((uint64_t)src < (uint64_t)n && (uint64_t)b < (uint64_t)n_blocks) {        // a plan that is not one reads and writes nothing
+            blk = (int)b;
+            lvl = levels[src];
+            if (lvl >= RAHT_LEVELS) { atomicAdd(&status[0], 1); lvl = RAHT_LEVELS - 1; }
+        }
+    }
+    for (int d = 1; d < 64; d <<= 1) {
+        const int other_lvl = __shfl_up(lvl, d, 64), other_blk = __shfl_up(blk, d, 64);
+        if (lane >= d && other_blk == blk) lvl = min(lvl, other_lvl);
+    }
+    const int next_blk = __shfl_down(blk, 1, 64);
+    if (blk >= 0 && (lane == 63 || next_blk != blk)) atomicMin(&block_level[blk], lvl);
+}
+
+// lev[i] = coeff_level[i] = block_level[block_of_row[i]]: the walk's working array, and the level of the rows no step owns.  One
+// thread per four rows, so that the byte-wide output leaves as one 32-bit word per thread where the pointer allows it.
+__global__ __launch_bounds__(RAHT_BLOCK) void raht_expand_levels_kernel(const int32_t* __restrict__ block_level, int64_t n_blocks,
+                                                                        const int32_t* __restrict__ block_of_row, int64_t n,
+                                                                        int32_t* __restrict__ lev, uint8_t* __restrict__ coeff_level, int word_stores) {
+    const int64_t i0 = ((int64_t)blockIdx.x * RAHT_BLOCK + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    uint32_t word = 0;
+    const int rows = (int)min((int64_t)4, n - i0);
+    for (int k = 0; k < rows; ++k) {
+        const int64_t b = block_of_row[i0 + k];
+        int v = (uint64_t)b < (uint64_t)n_blocks ? block_level[b] : RAHT_LEVELS - 1;
+        v = min(max(v, 0), RAHT_LEVELS - 1);
+        lev[i0 + k] = v;
+        word |= (uint32_t)v << (8 * k);
+    }
+    if (word_stores && rows == 4) {
+        *reinterpret_cast<uint32_t*>(coeff_level + i0) = word;
+    } else {
+        for (int k = 0; k < rows; ++k) coeff_level[i0 + k] = (uint8_t)(word >> (8 * k));
+    }
+}
+
+// One pair of a step of the level walk: the coefficient of row r summarises the rows [left[r], r + w1[r]), and its level is the
+// finest (smallest) level inside them; lev[left] carries the minimum of the merged node upward.  Rows as in raht_pair: within a
+// step no row belongs to two pairs.
+__device__ __forceinline__ void raht_level_pair(int32_t* lev, uint8_t* coeff_level, int64_t n, const int32_t* __restrict__ rows, int64_t j,
+                                                const int32_t* __restrict__ left) {
+    const int64_t r = rows[j];
+    if ((uint64_t)r >= (uint64_t)n) return;
+    const int64_t l = left[r];
+    if ((uint64_t)l >= (uint64_t)n || l == r) return;
+    const int m = min(lev[l], lev[r]);
+    coeff_level[r] = (uint8_t)m;
+    lev[l] = m;
+}
+
+__global__ __launch_bounds__(RAHT_BLOCK) void raht_level_step_kernel(int32_t* __restrict__ lev, uint8_t* __restrict__ coeff_level, int64_t n,
+                                                                     const int32_t* __restrict__ rows, int64_t m, const int32_t* __restrict__ left) {
+    const int64_t j = (int64_t)blockIdx.x * RAHT_BLOCK + threadIdx.x;
+    if (j < m) raht_level_pair(lev, coeff_level, n, rows, j, left);
+}
+
+// the folded top steps [lo, hi) of the walk in one workgroup, then the DC's level: lev[0] after the last step, the global minimum
+__global__ __launch_bounds__(RAHT_FOLD_BLOCK) void raht_level_fold_kernel(int32_t* lev, uint8_t* coeff_level, int64_t n, const int32_t* __restrict__ step_rows,
+                                                                          RahtOffsets off, int lo, int hi, const int32_t* __restrict__ left) {
+    for (int s = lo; s < hi; ++s) {
+        const int64_t work = off.at[s + 1] - off.at[s];
+        for (int64_t j = threadIdx.x; j < work; j += RAHT_FOLD_BLOCK) raht_level_pair(lev, coeff_level, n, step_rows + off.at[s], j, left);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) coeff_level[0] = (uint8_t)lev[0];
+}
+
+struct RahtSteps { double at[RAHT_LEVELS]; };
+
+// thread = (row, channel): symbol = rint(coefficient / step[level of the row]), ties to even, a true division
+__global__ __launch_bounds__(RAHT_BLOCK) void raht_quantize_kernel(const double* __restrict__ coeffs, int64_t n, int c, const uint8_t* __restrict__ coeff_level,
+                                                                   RahtSteps steps, int32_t* __restrict__ symbols, int32_t* __restrict__ status) {
+    const int64_t t = (int64_t)blockIdx.x * RAHT_BLOCK + threadIdx.x;
+    if (t >= n * c) return;
+    const int64_t row = (t >> 32) ? t / c : (int64_t)((uint32_t)t / (uint32_t)c);
+    const int level = min((int)coeff_level[row], RAHT_LEVELS - 1);
+    const double q = rint(coeffs[t] / steps.at[level]);
+    const bool ok = fabs(q) < 268435456.0;             // 2^28; false for a NaN too
+    if (!ok) atomicAdd(&status[0], 1);
+    symbols[t] = ok ? (int32_t)q : 0;
+}
+
+__global__ __launch_bounds__(RAHT_BLOCK) void raht_dequantize_kernel(const int32_t* __restrict__ symbols, int64_t n, int c, const uint8_t* __restrict__ coeff_level,
+                                                                     RahtSteps steps, double* __restrict__ coeffs) {
+    const int64_t t = (int64_t)blockIdx.x * RAHT_BLOCK + threadIdx.x;
+    if (t >= n * c) return;
+    const int64_t row = (t >> 32) ? t / c : (int64_t)((uint32_t)t / (uint32_t)c);
+    const int level = min((int)coeff_level[row], RAHT_LEVELS - 1);
+    coeffs[t] = (double)symbols[t] * steps.at[level];
+}
+
+static bool raht_steps_ok(const double* steps_host, RahtSteps* out) {
+    for (int l = 0; l < RAHT_LEVELS; ++l) {
+        if (!(steps_host[l] > 0.0) || !std::isfinite(steps_host[l])) return false;
+        out->at[l] = steps_host[l];
+    }
+    return true;
+}
+
 }  // namespace pcc
 
 using namespace pcc;
@@ -241,6 +374,99 @@ int pcc_raht_transform(double* values, int64_t n, int32_t c, const int32_t* left
     }
     if (!inverse && folded)
         hipLaunchKernelGGL(raht_fold_kernel<false>, dim3(1), dim3(RAHT_FOLD_BLOCK), 0, st, values, n, (int)c, step_rows, off, fold, nsteps, left, w0, w1);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+int pcc_raht_blocks(const int32_t* step, int64_t n, int32_t block_log2, int32_t* block_of_row, int32_t* n_blocks, void* scratch,
+                    int64_t scratch_bytes, void* stream) {
+    PCC_REQUIRE(n >= 1 && n < (1ll << 31) - 1, "pcc_raht_blocks: bad row count %lld", (long long)n);
+    PCC_REQUIRE(block_log2 >= 0 && block_log2 <= RAHT_MAX_DEPTH, "pcc_raht_blocks: block_log2 %d outside 0..%d", block_log2, RAHT_MAX_DEPTH);
+    PCC_REQUIRE(step && block_of_row && n_blocks && scratch, "pcc_raht_blocks: null step, output or scratch");
+    PCC_REQUIRE(scratch_bytes >= pcc_raht_scratch_bytes(n), "pcc_raht_blocks: scratch of %lld bytes, needs %lld", (long long)scratch_bytes,
+                (long long)pcc_raht_scratch_bytes(n));
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(raht_block_flags_kernel, dim3(blocks_for(n, RAHT_BLOCK)), dim3(RAHT_BLOCK), 0, st, step, n, 3 * (int)block_log2, block_of_row);
+    // the inclusive scan of the block-start flags, in place: row 0 carries no flag, so the sums are the block indices
+    const int rc = scan_flags(block_of_row, n, block_of_row, reinterpret_cast<int32_t*>(scratch), nullptr, 1, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(raht_block_count_kernel, dim3(1), dim3(64), 0, st, (const int32_t*)block_of_row, n, n_blocks);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+int pcc_raht_block_levels(const uint8_t* levels, const int32_t* perm, const int32_t* block_of_row, int64_t n, int64_t n_blocks,
+                          int32_t* block_level, int32_t* status, void* stream) {
+    PCC_REQUIRE(n >= 1 && n < (1ll << 31) - 1, "pcc_raht_block_levels: bad row count %lld", (long long)n);
+    PCC_REQUIRE(n_blocks >= 1 && n_blocks <= n, "pcc_raht_block_levels: %lld blocks for %lld rows", (long long)n_blocks, (long long)n);
+    PCC_REQUIRE(levels && perm && block_of_row && block_level && status, "pcc_raht_block_levels: null levels, plan, output or status");
+    hipStream_t st = as_stream(stream);
+    PCC_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(raht_fill_kernel, dim3(blocks_for(n_blocks, RAHT_BLOCK)), dim3(RAHT_BLOCK), 0, st, block_level, n_blocks, RAHT_LEVELS - 1);
+    hipLaunchKernelGGL(raht_block_levels_kernel, dim3(blocks_for(n, RAHT_BLOCK)), dim3(RAHT_BLOCK), 0, st, levels, perm, block_of_row, n, n_blocks,
+                       block_level, status);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+int pcc_raht_coeff_levels(const int32_t* block_level, const int32_t* block_of_row, int64_t n, int64_t n_blocks, const int32_t* left,
+                          const int32_t* step_rows, const int32_t* step_offsets_host, int32_t depth, uint8_t* coeff_level, int32_t* lev,
+                          void* stream) {
+    PCC_REQUIRE(n >= 1 && n < (1ll << 31) - 1, "pcc_raht_coeff_levels: bad row count %lld", (long long)n);
+    PCC_REQUIRE(n_blocks >= 1 && n_blocks <= n, "pcc_raht_coeff_levels: %lld blocks for %lld rows", (long long)n_blocks, (long long)n);
+    PCC_REQUIRE(depth >= 0 && depth <= RAHT_MAX_DEPTH, "pcc_raht_coeff_levels: depth %d outside 0..%d", depth, RAHT_MAX_DEPTH);
+    PCC_REQUIRE(block_level && block_of_row && left && step_rows && step_offsets_host && coeff_level && lev,
+                "pcc_raht_coeff_levels: null levels, plan, output or scratch");
+    const int nsteps = 3 * depth;
+    PCC_REQUIRE(step_offsets_host[0] == 0, "pcc_raht_coeff_levels: step_offsets[0] = %d, not 0", step_offsets_host[0]);
+    for (int s = 0; s < nsteps; ++s)
+        PCC_REQUIRE(step_offsets_host[s] <= step_offsets_host[s + 1] && step_offsets_host[s + 1] <= n,
+                    "pcc_raht_coeff_levels: step_offsets[%d] = %d after %d with %lld rows", s + 1, step_offsets_host[s + 1], step_offsets_host[s],
+                    (long long)n);
+    hipStream_t st = as_stream(stream);
+    const int word_stores = (reinterpret_cast<uintptr_t>(coeff_level) & 3) == 0;
+    hipLaunchKernelGGL(raht_expand_levels_kernel, dim3(blocks_for((n + 3) / 4, RAHT_BLOCK)), dim3(RAHT_BLOCK), 0, st, block_level, n_blocks,
+                       block_of_row, n, lev, coeff_level, word_stores);
+    // the launch plan of pcc_raht_transform (forward): one launch per non-empty step, the small steps at the top in one workgroup
+    RahtOffsets off;
+    for (int s = 0; s <= nsteps; ++s) off.at[s] = step_offsets_host[s];
+    int fold = nsteps;
+    while (fold > 0 && off.at[fold] - off.at[fold - 1] <= RAHT_FOLD_ROWS) --fold;
+    if (nsteps - fold < 2 || off.at[nsteps] == off.at[fold]) fold = nsteps;
+    for (int s = 0; s < fold; ++s) {
+        const int64_t m = (int64_t)off.at[s + 1] - off.at[s];
+        if (m == 0) continue;
+        hipLaunchKernelGGL(raht_level_step_kernel, dim3(blocks_for(m, RAHT_BLOCK)), dim3(RAHT_BLOCK), 0, st, lev, coeff_level, n, step_rows + off.at[s], m, left);
+    }
+    // (with nothing folded the launch runs no step and only writes the DC's level)
+    hipLaunchKernelGGL(raht_level_fold_kernel, dim3(1), dim3(RAHT_FOLD_BLOCK), 0, st, lev, coeff_level, n, step_rows, off, fold, nsteps, left);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+int pcc_raht_quantize(const double* coeffs, int64_t n, int32_t c, const uint8_t* coeff_level, const double* steps_host, int32_t* symbols,
+                      int32_t* status, void* stream) {
+    PCC_REQUIRE(n >= 1 && n < (1ll << 31) - 1, "pcc_raht_quantize: bad row count %lld", (long long)n);
+    PCC_REQUIRE(c >= 1 && c <= RAHT_MAX_CHANNELS, "pcc_raht_quantize: %d channels outside 1..%d", c, RAHT_MAX_CHANNELS);
+    PCC_REQUIRE(coeffs && coeff_level && steps_host && symbols && status, "pcc_raht_quantize: null coefficients, levels, steps, output or status");
+    RahtSteps steps;
+    PCC_REQUIRE(raht_steps_ok(steps_host, &steps), "pcc_raht_quantize: a step of the table is not a positive finite number");
+    hipStream_t st = as_stream(stream);
+    PCC_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(raht_quantize_kernel, dim3(blocks_for(n * c, RAHT_BLOCK)), dim3(RAHT_BLOCK), 0, st, coeffs, n, (int)c, coeff_level, steps, symbols, status);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+int pcc_raht_dequantize(const int32_t* symbols, int64_t n, int32_t c, const uint8_t* coeff_level, const double* steps_host, double* coeffs,
+                        void* stream) {
+    PCC_REQUIRE(n >= 1 && n < (1ll << 31) - 1, "pcc_raht_dequantize: bad row count %lld", (long long)n);
+    PCC_REQUIRE(c >= 1 && c <= RAHT_MAX_CHANNELS, "pcc_raht_dequantize: %d channels outside 1..%d", c, RAHT_MAX_CHANNELS);
+    PCC_REQUIRE(symbols && coeff_level && steps_host && coeffs, "pcc_raht_dequantize: null symbols, levels, steps or output");
+    RahtSteps steps;
+    PCC_REQUIRE(raht_steps_ok(steps_host, &steps), "pcc_raht_dequantize: a step of the table is not a positive finite number");
+    hipLaunchKernelGGL(raht_dequantize_kernel, dim3(blocks_for(n * c, RAHT_BLOCK)), dim3(RAHT_BLOCK), 0, as_stream(stream), symbols, n, (int)c, coeff_level,
+                       steps, coeffs);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
 }

@@ -120,19 +120,42 @@ def _pcqm_columns(metric):
     return {k: v for k, v in res.items() if k.startswith("pcqm_")}
 
 
-def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, colorspace="yuv", pcqm=False, contexts=False):
+# the qsteps evaluate_view_dependent searches for an anchor row that matches a model row's bytes: from a quarter of an 8-bit level
+# up to four times the colour range, where little but the DC survives, so that a model row of very low rate still finds its match
+ANCHOR_MATCH_QSTEPS = (0.25 / 255, 1024 / 255)
+
+
+def _levels_bytes(stream):
+    """the bytes a PCA1 stream spends on block levels: the levels payload of its PCR2 attributes, 0 for PCR1"""
+    import struct
+    from . import raht
+    (glen,) = struct.unpack("<I", stream[8:12])
+    attributes = stream[12 + glen:]
+    if attributes[:4] != raht.MAGIC_REGION:
+        return 0
+    return int(struct.unpack("<I", attributes[25:29])[0])
+
+
+def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, colorspace="yuv", pcqm=False, contexts=False, quality=None,
+                    block_log2=3, span=24):
     """one row of the sweep table for the octree + RAHT anchor codec (anchor.py) at quantisation step ``qstep``: the keys of
     ``evaluate_frame``'s row without the quality-map pair, plus ``qstep`` and ``codec``.  ``bpp`` counts the whole PCA1 stream;
     the geometry is lossless, so ``sym_p2p_psnr`` is inf and ``n_decoded`` equals ``n_source``.  ``downsample`` and
     ``resolution`` mean what they mean in ``evaluate_frame``: the anchor's lossy-geometry rate points are coarser grids; so does
-    ``pcqm``.  ``contexts``: the anchor's geometry as PCO2 (octree.py: neighbour contexts) instead of PCO1."""
+    ``pcqm``.  ``contexts``: the anchor's geometry as PCO2 (octree.py: neighbour contexts) instead of PCO1.
+
+    ``quality`` (a per-point map as ``anchor.compress`` takes it, with ``block_log2`` and ``span``): region-wise quantisation;
+    with ``downsample`` the map follows each voxel's first point.  The row gains ``levels_bytes``, what the stream spends on
+    the block levels (0 without a map)."""
     from . import anchor
     n_input = None
     if downsample is not None:
         if not float(downsample) >= 1.0:
             raise ValueError(f"downsample {downsample}: a factor of at least 1")
         n_input = int(data["src"]["points"].shape[1])
-        data, _, _ = downsample_frame(data, downsample, device)
+        if quality is not None:
+            quality = torch.as_tensor(quality).reshape(n_input, -1)[:, -1]
+        data, quality, _ = downsample_frame(data, downsample, device, quality)
         resolution = max(1, int(round((resolution + 1) / float(downsample))) - 1)
     points = data["src"]["points"].to(device, dtype=torch.float)
     colors = data["src"]["colors"].to(device, dtype=torch.float)
@@ -140,7 +163,7 @@ def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, color
 
     torch.cuda.synchronize()
     t0 = time.time()
-    stream = anchor.compress(src, qstep, colorspace=colorspace, contexts=contexts)
+    stream = anchor.compress(src, qstep, colorspace=colorspace, contexts=contexts, quality=quality, block_log2=block_log2, span=span)
     torch.cuda.synchronize()
     t_c = time.time() - t0
 
@@ -153,7 +176,7 @@ def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, color
     metric = PointCloudMetric(src, rec, resolution=resolution, device=device)
     res, _ = metric.compute_pointcloud_metrics(drop_duplicates=True)
     row = {"codec": "octree+raht", "qstep": float(qstep), "bpp": len(stream) * 8 / src.shape[0], "t_compress": t_c, "t_decompress": t_d,
-           "n_source": int(src.shape[0]), "n_decoded": int(rec.shape[0]),
+           "n_source": int(src.shape[0]), "n_decoded": int(rec.shape[0]), "levels_bytes": _levels_bytes(stream),
            "sym_p2p_psnr": res["sym_psnr_mse"], "sym_y_psnr": res["sym_y_psnr"], "sym_u_psnr": res["sym_u_psnr"],
            "sym_v_psnr": res["sym_v_psnr"]}
     if pcqm:
@@ -169,7 +192,7 @@ def _extent(points, axis):
 
 
 def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path, view="front", H=1024, W=512, gradient=None, roi=None,
-                            save_images=False, details=None, facing=None, visibility=None, camera=None):
+                            save_images=False, details=None, facing=None, visibility=None, camera=None, anchor=None):
     """The three rows of evaluate_view_dep.py:139-301 for one frame -> {"uniform": row, "view": row, "roi": row}, each row
     {"bpp", "q_a", "q_g", "key", "psnr", "ssim"}.
 
@@ -198,7 +221,23 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
     tagged "camera").  The default gradient runs along the camera's dominant front axis and the default region of interest
     along its dominant right axis; ``facing`` defaults its ``camera`` to the camera's position; ``visibility`` takes ``cameras``
     (a list of render.Camera; ``[camera]`` when left out) in place of ``views`` and uses render.camera_visibility, with
-    ``point_size`` a voxel edge (1.0).  With ``camera=None`` nothing changes."""
+    ``point_size`` a voxel edge (1.0).  With ``camera=None`` nothing changes.
+
+    ``anchor`` (a dict): a conventional baseline for every row.  After the model's rows one row ``"anchor_<key>"`` per map is
+    appended (uniform, view, roi, and facing / visible when present): the source coded by the octree + RAHT anchor codec
+    (anchor.py) with that row's score as its quality map (score 1 at the row's qstep, lower scores coarser; the uniform row has
+    no map and is the plain PCR1 stream), rendered and judged by the same view or camera in the source's frame.  Its keys:
+    ``match`` (True: every anchor row is searched, anchor.compress_to_bytes over ANCHOR_MATCH_QSTEPS, to at most the bytes of
+    the model's row with the same key; False: it is coded at ``qstep``), ``qstep`` (needed without ``match``), ``block_log2``, ``span``, ``colorspace``,
+    ``contexts`` (anchor.compress's).  The rows carry ``"codec": "anchor"``, the ``qstep`` used, ``reached`` (False when even
+    the coarsest step of the search is above the bytes to match), ``levels_bytes``, and q_a = q_g = None.  Images are saved as
+    ``anchor_<key>_<tag>.png``.  With ``anchor=None`` nothing changes."""
+    if anchor is not None:
+        unknown = set(anchor) - {"qstep", "match", "block_log2", "span", "colorspace", "contexts"}
+        if unknown:
+            raise ValueError("anchor: unknown keys %s" % sorted(unknown))
+        if not anchor.get("match", True) and anchor.get("qstep") is None:
+            raise ValueError("anchor: without match the rows need a qstep")
     if camera is not None:
         if not isinstance(camera, render.Camera):
             raise ValueError("camera is a render.Camera, got %r" % (camera,))
@@ -279,4 +318,25 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
             write_png(os.path.join(img_dir, "%s_a%s_g%s_%s.png" % (key, str(q_a), str(q_g), tag)), img)
         if details is not None:
             details[key] = (rec, img)
+    if anchor is not None:
+        from . import anchor as anchor_codec
+        match, qstep = anchor.get("match", True), anchor.get("qstep")
+        kw = {k: anchor[k] for k in ("block_log2", "span", "colorspace", "contexts") if k in anchor}
+        n = int(src.shape[0])
+        for key, score in maps.items():
+            if match:
+                stream, step, reached = anchor_codec.compress_to_bytes(src, int(round(rows[key]["bpp"] * n / 8)), quality=score,
+                                                                       qstep_lo=ANCHOR_MATCH_QSTEPS[0], qstep_hi=ANCHOR_MATCH_QSTEPS[1], **kw)
+            else:
+                stream, step, reached = anchor_codec.compress(src, qstep, quality=score, **kw), float(qstep), True
+            rec = anchor_codec.decompress(stream, device)
+            img = draw(rec)
+            m = render.view_metrics(ref_img, img)
+            name = "anchor_" + key
+            rows[name] = {"bpp": len(stream) * 8 / n, "q_a": None, "q_g": None, "key": name, "psnr": m["psnr"], "ssim": m["ssim"],
+                          "codec": "anchor", "qstep": step, "reached": reached, "levels_bytes": _levels_bytes(stream)}
+            if save_images:
+                write_png(os.path.join(img_dir, "%s_%s.png" % (name, tag)), img)
+            if details is not None:
+                details[name] = (rec, img)
     return rows

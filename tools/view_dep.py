@@ -17,7 +17,10 @@ usage: view_dep.py [config1 | config2 | frame.ply] [--out DIR] [--view front|sid
                    of the active view table, the judged view when left out)
                    [--camera X,Y,Z --look-at X,Y,Z --fov 30]     (a pinhole camera at a position in place of the axis view:
                    every image is render.render_camera's at --height x --width, --fov the full vertical angle in degrees; --look-at
-                   defaults to the middle of the frame's bounding box; --visibility then asks render.camera_visibility of this camera)"""
+                   defaults to the middle of the frame's bounding box; --visibility then asks render.camera_visibility of this camera)
+                   [--anchor [--anchor-qstep Q] [--anchor-span 24]]     (one row "anchor_<key>" per row: the octree + RAHT anchor
+                   codec with the row's map as region-wise quantisation, searched to the bytes of the model's row, or coded at
+                   --anchor-qstep (in 1/255 units) when that is given; the CSV gains the columns codec and qstep)"""
 import argparse
 import csv
 import json
@@ -67,6 +70,9 @@ def main():
     ap.add_argument("--camera", type=xyz, metavar="X,Y,Z", help="judge from a pinhole camera at this position instead of the axis view")
     ap.add_argument("--look-at", type=xyz, metavar="X,Y,Z", help="the point the camera looks at (default: the middle of the bounding box)")
     ap.add_argument("--fov", type=float, default=30.0, help="the camera's full vertical field of view in degrees")
+    ap.add_argument("--anchor", action="store_true", help="add one anchor-codec row per row, matched to the model row's bytes")
+    ap.add_argument("--anchor-qstep", type=float, help="code the anchor rows at this step (1/255 units) instead of matching bytes")
+    ap.add_argument("--anchor-span", type=int, default=24, help="levels between quality 1 and quality 0 (raht.quality_levels)")
     ap.add_argument("--repeat", type=int, default=0, help="time render_view and view_metrics over N further calls")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
@@ -103,19 +109,26 @@ def main():
         table = render.VIEWS_MVUB if a.mvub else render.VIEWS
         visibility = {"views": [table[name] for name in (a.vis_views or [a.view])], "tolerance": a.vis_tolerance, "falloff": a.vis_falloff,
                       "floor": a.vis_floor}
+    anchor = None
+    if a.anchor:
+        anchor = {"span": a.anchor_span}
+        if a.anchor_qstep is not None:
+            anchor.update(match=False, qstep=a.anchor_qstep / 255.0)
     t0 = time.time()
     rows = evaluate_view_dependent(a.experiment, model, data, a.q_a, a.q_g, dev, a.out, view=view if a.mvub else a.view, H=a.height,
                                    W=a.width, gradient=gradient, roi=roi, save_images=True, details=details, facing=facing,
-                                   visibility=visibility, camera=camera)
+                                   visibility=visibility, camera=camera, anchor=anchor)
     t_all = time.time() - t0
+    anchor_rows = {k: r for k, r in rows.items() if k.startswith("anchor_")}
     path = os.path.join(a.out, a.experiment, "view_dep.csv")
     with open(path, "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=["bpp", "q_a", "q_g", "key", "psnr", "ssim"])
+        w = csv.DictWriter(f, fieldnames=["bpp", "q_a", "q_g", "key", "psnr", "ssim"] + (["codec", "qstep"] if a.anchor else []),
+                           extrasaction="ignore")
         w.writeheader()
         for row in rows.values():
             w.writerow(row)
     for key, row in rows.items():
-        print("%-8s bpp %.4f  view psnr %.3f dB  view ssim %.5f" % (key, row["bpp"], row["psnr"], row["ssim"]))
+        print("%-*s bpp %.4f  view psnr %.3f dB  view ssim %.5f" % (14 if a.anchor else 8, key, row["bpp"], row["psnr"], row["ssim"]))
     result = {"frame": a.frame, "n_points": int(pts.shape[0]), "H": a.height, "W": a.width, "view": a.view, "t_three_rows_s": t_all}
     if camera is not None:
         result["view"] = "camera"
@@ -123,7 +136,11 @@ def main():
         result["camera"] = {"position": list(a.camera), "look_at": list(look_at), "fov_y": a.fov, "pos_q": list(q.pos_q),
                             "axes_q": [list(r) for r in q.axes_q], "focal_q": q.focal_q, "near_q": q.near_q}
     if a.facing or a.visibility:
-        result["t_%s_rows_s" % {4: "four", 5: "five"}[len(rows)]] = result.pop("t_three_rows_s")
+        result["t_%s_rows_s" % {4: "four", 5: "five"}[len(rows) - len(anchor_rows)]] = result.pop("t_three_rows_s")
+    if a.anchor:
+        result["t_with_anchor_rows_s"] = result.pop(next(k for k in result if k.startswith("t_") and k.endswith("_rows_s")))
+        result["anchor"] = {k: {"qstep_255": r["qstep"] * 255.0, "reached": r["reached"], "levels_bytes": r["levels_bytes"]}
+                            for k, r in anchor_rows.items()}
     if a.visibility:
         behind = details["visibility"][0]
         result["visibility"] = {"views": ["camera"] if camera is not None else (a.vis_views or [a.view]), "tolerance": a.vis_tolerance, "falloff": a.vis_falloff, "floor": a.vis_floor,
