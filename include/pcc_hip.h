@@ -650,8 +650,43 @@ int pcc_pcqm_features(const int32_t* coords_r, int64_t n_r, const uint64_t* keys
  * Both refuse before any launch (PCC_ERR_ARG): a null pointer (cloud or outputs with n > 0, camera arrays,
  * background, z-buffer, image), a short z-buffer, any value outside the table above, n above 2^32 - 2.  Not a lens
  * model: no distortion, square splats, no anti-aliasing, and holes open once a voxel projects beyond 16 pixels.
+ *
+ * pcc_view_buffers and pcc_camera_buffers expose the z-buffer those views draw (the arguments of pcc_view_visibility /
+ * pcc_camera_visibility without `accumulate`; clear, splat, then one thread per pixel):
+ *   index[H,W] = the row the pixel shows under the renderer's full winner rule, -1 for background
+ *   depth[H,W] = d = front . p of that row for the orthographic view, its depth key dk for the camera;
+ *                PCC_VIS_OFFSCREEN for background
+ * n == 0 is valid: every pixel is background.  Refused before any launch as their visibility counterparts, and on a
+ * null index or depth.
+ *
+ * pcc_view_sample and pcc_camera_sample carry an image BACK to the points (screen-space quality maps): the clear and
+ * splat of the visibility entries, then one thread per point walks its clipped splat again.  image: int32
+ * [H,W,channels], channels 1 .. PCC_SAMPLE_MAX_CHANNELS.  A pixel of row i's splat COUNTS for row i when
+ *   tolerance == PCC_SAMPLE_OWN: its word is row i's own (the pixels that show the point; their number is `won`);
+ *   tolerance >= 0: (d_win(pixel) - d_i) <= tolerance for the view, (dk_i - dk_front(pixel)) >> 8 <= tolerance for the
+ *                   camera: the quantity whose minimum over the splat is `behind`, so the pixel looks at the surface
+ *                   the point belongs to, within `tolerance` whole voxels, and count[i] > 0 <=> behind[i] <= tolerance.
+ * Per row, over the counted pixels:
+ *   total[n,channels] int64 = the sum of the image;  count[n] int32 = their number;
+ *   peak[n,channels]  int32 = the maximum, PCC_SAMPLE_NONE when nothing counted.
+ * A row that is not drawn, or whose splat lies wholly outside the image: count 0, total 0, peak PCC_SAMPLE_NONE.
+ * accumulate != 0 folds into what the arrays hold: sum / sum / max (a thread owns its row: a plain read-modify-write).
+ * At most 256 pixels count per row and call, so |total| grows by less than 2^39 per call.  All integer, bitwise
+ * reproducible, no atomics beyond the splat's.  n == 0 launches nothing and touches no array.  Refused before any
+ * launch: the visibility entries' conditions, channels outside 1 .. 4, tolerance below -1, a null image, null outputs
+ * with n > 0.  Not a texture unit: no sub-pixel or bilinear sampling, integer images only.
+ *
+ * pcc_image_compare_masked is pcc_image_compare restricted to a region: mask uint8 [H,W], nonzero = inside.  out[0..2]
+ * run over the masked pixels only, out[3..5] over the windows of the crop whose centre pixel (top-left + 3, + 3) is
+ * masked; out[6], out[7] stay over the whole of `ref` (the data-range rule does not change with the mask).  The same
+ * tile kernel, so the additions happen in the same order: with an all-nonzero mask out[0..5] equal
+ * pcc_image_compare's bit for bit.  The caller divides by the numbers of masked pixels and windows.  Refused as
+ * pcc_image_compare, and on a null mask.
  * ------------------------------------------------------------------------------------- */
 #define PCC_VIS_OFFSCREEN 2147483647
+#define PCC_SAMPLE_MAX_CHANNELS 4
+#define PCC_SAMPLE_OWN (-1)
+#define PCC_SAMPLE_NONE (-2147483648)
 int64_t pcc_render_scratch_bytes(int32_t H, int32_t W);
 int pcc_render_view(const int32_t* coords, const uint8_t* rgb8, int64_t n, const int32_t* right, const int32_t* up,
                     const int32_t* front, int32_t u_min, int32_t v_max, int32_t ox, int32_t oy, int32_t scale,
@@ -674,6 +709,23 @@ int32_t pcc_image_compare_tile(void);
 int64_t pcc_image_compare_scratch_bytes(int32_t H, int32_t W);
 int pcc_image_compare(const uint8_t* ref, const uint8_t* img, int32_t H, int32_t W, void* scratch,
                       int64_t scratch_bytes, double* out, void* stream);
+int pcc_image_compare_masked(const uint8_t* ref, const uint8_t* img, const uint8_t* mask, int32_t H, int32_t W,
+                             void* scratch, int64_t scratch_bytes, double* out, void* stream);
+int pcc_view_buffers(const int32_t* coords, int64_t n, const int32_t* right, const int32_t* up, const int32_t* front,
+                     int32_t u_min, int32_t v_max, int32_t ox, int32_t oy, int32_t scale, int32_t point_size,
+                     int32_t H, int32_t W, void* scratch, int64_t scratch_bytes, int32_t* index, int32_t* depth,
+                     void* stream);
+int pcc_camera_buffers(const int32_t* coords, int64_t n, const int32_t* pos_q, const int32_t* axes_q, int32_t focal_q,
+                       int32_t near_q, int32_t H, int32_t W, int32_t ps_q, void* scratch, int64_t scratch_bytes,
+                       int32_t* index, int32_t* depth, void* stream);
+int pcc_view_sample(const int32_t* coords, int64_t n, const int32_t* right, const int32_t* up, const int32_t* front,
+                    int32_t u_min, int32_t v_max, int32_t ox, int32_t oy, int32_t scale, int32_t point_size, int32_t H,
+                    int32_t W, void* scratch, int64_t scratch_bytes, int32_t accumulate, const int32_t* image,
+                    int32_t channels, int32_t tolerance, int64_t* total, int32_t* count, int32_t* peak, void* stream);
+int pcc_camera_sample(const int32_t* coords, int64_t n, const int32_t* pos_q, const int32_t* axes_q, int32_t focal_q,
+                      int32_t near_q, int32_t H, int32_t W, int32_t ps_q, void* scratch, int64_t scratch_bytes,
+                      int32_t accumulate, const int32_t* image, int32_t channels, int32_t tolerance, int64_t* total,
+                      int32_t* count, int32_t* peak, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Entropy model, device side (compressai EntropyBottleneck / GaussianConditional,

@@ -25,12 +25,23 @@
 // pcc_render_camera and pcc_camera_visibility the pinhole CameraView at a position (a perspective projection in int64, key =
 // 0x7FFFFFFF - depth key in 1/256 voxel, gap shift 8), whose walk back also returns each point's depth key.
 //
+// pcc_view_buffers / pcc_camera_buffers expose the z-buffer itself: the same clear and splat, then buffers_kernel<View>, one thread
+// per pixel, unpacks the word into the row it shows (-1 for background) and its depth (View::depth_of the key).
+//
+// pcc_view_sample / pcc_camera_sample carry an IMAGE back to the points (screen-space quality maps): the same clear and splat, then
+// sample_kernel<View, C>, one thread per point, walks its splat as gather_kernel does and adds up (and takes the maximum of) a
+// C-channel int32 image over the pixels that count for the point: its own pixels (tolerance PCC_SAMPLE_OWN) or the pixels whose
+// front is at most `tolerance` whole voxels in front of it, the quantity whose minimum is `behind`.  All integer, no atomics
+// beyond the splat's.
+//
 // pcc_image_compare replaces rgb2yuv +peak_signal_noise_ratio + structural_similarity (evaluate_view_dep.py:196-204) by
 // their raw sums in float64: one workgroup per IC_TILE x IC_TILE tile converts the tile and its 6-pixel apron to YUV one
 // channel at a time into LDS, adds the squared differences of the pixels it owns and the SSIM map values of the 7 x 7
 // windows whose top-left pixel it owns, reduces them over a fixed tree and stores its eight partials; a second kernel
 // adds the partials in ascending workgroup order.  No float atomics: the result is bitwise reproducible.  Separate
-// multiplies and adds throughout (the library is built with -ffp-contract=off).
+// multiplies and adds throughout (the library is built with -ffp-contract=off).  pcc_image_compare_masked is the same tile
+// kernel with a mask (a template flag): a pixel adds its squared differences only when it is masked, a window its SSIM value
+// only when its centre pixel is; nothing else changes, so the additions happen in the same order.
 #include "common.h"
 
 namespace pcc {
@@ -67,6 +78,9 @@ struct RenderView {
     int32_t r[3], u[3], f[3];
     int32_t u_min, v_max, ox, oy, scale, point_size, H, W;
 
+    // what pcc_view_buffers reports for a key: d = front . p
+    static __device__ __forceinline__ int32_t depth_of(uint32_t key) { return (int32_t)key - RENDER_DEPTH_BIAS; }
+
     // false when the row draws nothing: a coordinate out of range
     __device__ __forceinline__ bool project(const int4 c, Splat& out) const {
         if (!coord_in_range(0, c.y, c.z, c.w)) return false;
@@ -102,6 +116,9 @@ struct CameraView {
     static constexpr bool HAS_DEPTH = true;
     int32_t pos[3], ax[3][3];
     int32_t focal, near, ps, H, W;
+
+    // what pcc_camera_buffers reports for a key: the depth key dk
+    static __device__ __forceinline__ int32_t depth_of(uint32_t key) { return (int32_t)(0x7FFFFFFFu - key); }
 
     // false when the row draws nothing: a coordinate out of range, or in front of the near plane (behind the camera included)
     __device__ __forceinline__ bool project(const int4 c, Splat& out) const {
@@ -211,6 +228,71 @@ __global__ __launch_bounds__(256) void gather_kernel(const int32_t* __restrict__
     }
 }
 
+// ---- the z-buffer's planes: the row and the depth every pixel shows ----
+// One thread per pixel unpacks its word: index = the row under the full winner rule (the low half, 0xFFFFFFFF - row), depth =
+// View::depth_of(the key); a word of 0 (no splat reached the pixel) is background: -1 and PCC_VIS_OFFSCREEN.
+template <class View>
+__global__ __launch_bounds__(256) void buffers_kernel(const uint64_t* __restrict__ zbuf, int64_t npix, int32_t* __restrict__ index,
+                                                      int32_t* __restrict__ depth) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= npix) return;
+    const uint64_t word = zbuf[p];
+    index[p] = word == 0ull ? -1 : (int32_t)(0xFFFFFFFFu - (uint32_t)word);
+    depth[p] = word == 0ull ? PCC_VIS_OFFSCREEN : View::depth_of((uint32_t)(word >> 32));
+}
+
+// ---- back-projection: an image's values carried to the points ----
+// gather_kernel's walk.  A pixel of the splat counts for the row when its word is the row's own (tolerance == PCC_SAMPLE_OWN:
+// the pixels that show the point) or when (front key - own key) >> View::GAP_SHIFT <= tolerance (tolerance >= 0: the gap whose
+// minimum is `behind`, so count > 0 exactly where behind <= tolerance).  Over the counted pixels: total = the sum of the image
+// (int64: at most 256 pixels of |value| < 2^31 per call), count, peak = the maximum (PCC_SAMPLE_NONE when nothing counted).  C is
+// a template parameter so that the per-channel accumulators stay in registers (a run-time channel loop over a local array would
+// put them in scratch memory).  A thread owns its row: `accumulate` is a plain read-modify-write (sum, sum, max).
+template <class View, int C>
+__global__ __launch_bounds__(256) void sample_kernel(const int32_t* __restrict__ coords, int64_t n, View a, const uint64_t* __restrict__ zbuf,
+                                                     const int32_t* __restrict__ image, int32_t tolerance, int accumulate,
+                                                     int64_t* __restrict__ total, int32_t* __restrict__ count, int32_t* __restrict__ peak) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    const int4 c = reinterpret_cast<const int4*>(coords)[row];
+    int64_t sum[C];
+    int32_t top[C];
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) { sum[ch] = 0; top[ch] = PCC_SAMPLE_NONE; }
+    int32_t hits = 0;
+    Splat sp;
+    if (a.project(c, sp) && sp.r0 < sp.r1) {
+        const uint64_t own = splat_word(sp.key, row);
+        for (int32_t py = sp.r0; py < sp.r1; ++py) {
+            for (int32_t px = sp.c0; px < sp.c1; ++px) {
+                const int64_t at = (int64_t)py * a.W + px;
+                const uint64_t word = zbuf[at];
+                const int32_t gap = (int32_t)(((uint32_t)(word >> 32) - sp.key) >> View::GAP_SHIFT);
+                if (tolerance < 0 ? word != own : gap > tolerance) continue;
+                ++hits;
+#pragma unroll
+                for (int ch = 0; ch < C; ++ch) {
+                    const int32_t v = image[at * C + ch];
+                    sum[ch] += v;
+                    top[ch] = v > top[ch] ? v : top[ch];
+                }
+            }
+        }
+    }
+    if (accumulate) hits += count[row];
+    count[row] = hits;
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) {
+        if (accumulate) {
+            const int32_t old = peak[row * C + ch];
+            sum[ch] += total[row * C + ch];
+            top[ch] = old > top[ch] ? old : top[ch];
+        }
+        total[row * C + ch] = sum[ch];
+        peak[row * C + ch] = top[ch];
+    }
+}
+
 // ---- image metrics ----
 constexpr int IC_TILE = 32;                 // pixels a workgroup owns per side
 constexpr int IC_WIN = 7;                     // structural_similarity's window
@@ -243,8 +325,12 @@ __device__ __forceinline__ double ic_block_reduce(double v, int op, double* red)
     return red[0];
 }
 
+// MASKED: `mask` (uint8 [H, W], nonzero = inside) decides which pixels add their squared differences and which windows (by their
+// centre pixel, top-left + 3) their SSIM value; the reference's minimum and maximum stay over every pixel.
+template <bool MASKED>
 __global__ __launch_bounds__(IC_THREADS) void image_compare_tile_kernel(const uint8_t* __restrict__ ref, const uint8_t* __restrict__ img,
-                                                                        int H, int W, int tiles_x, double* __restrict__ partials) {
+                                                                        const uint8_t* __restrict__ mask, int H, int W, int tiles_x,
+                                                                        double* __restrict__ partials) {
     __shared__ double xs[IC_SPAN][IC_SPAN], ys[IC_SPAN][IC_SPAN];
     __shared__ double red[IC_THREADS];
     const int t = threadIdx.x;
@@ -263,8 +349,10 @@ __global__ __launch_bounds__(IC_THREADS) void image_compare_tile_kernel(const ui
                 x = ic_yuv(ref + at, ch);
                 y = ic_yuv(img + at, ch);
                 if (lr < IC_TILE && lc < IC_TILE) {        // a pixel this workgroup owns
-                    const double diff = x - y;
-                    sse[ch] = sse[ch] + diff * diff;
+                    if (!MASKED || mask[(int64_t)r * W + c]) {
+                        const double diff = x - y;
+                        sse[ch] = sse[ch] + diff * diff;
+                    }
                     lo = x < lo ? x : lo;
                     hi = x > hi ? x : hi;
                 }
@@ -276,6 +364,7 @@ __global__ __launch_bounds__(IC_THREADS) void image_compare_tile_kernel(const ui
         for (int o = t; o < IC_TILE * IC_TILE; o += IC_THREADS) {
             const int lr = o / IC_TILE, lc = o % IC_TILE;
             if (r0 + lr + IC_WIN > H || c0 + lc + IC_WIN > W) continue;      // the window leaves the image: not in the crop
+            if (MASKED && !mask[(int64_t)(r0 + lr + IC_WIN / 2) * W + (c0 + lc + IC_WIN / 2)]) continue;
             double sx = 0.0, sy = 0.0, sxx = 0.0, syy = 0.0, sxy = 0.0;
             for (int j = 0; j < IC_WIN; ++j) {
 #pragma unroll
@@ -425,6 +514,78 @@ static int look_back(const char* who, const View& a, const int32_t* coords, int6
     return PCC_OK;
 }
 
+// What the two buffers entries share: clear, splat, unpack.  n == 0 is valid: every pixel is background.
+template <class View>
+static int show_buffers(const char* who, const View& a, const int32_t* coords, int64_t n, void* scratch, int64_t scratch_bytes,
+                        int32_t* index, int32_t* depth, void* stream) {
+    PCC_REQUIRE(n == 0 || coords, "%s: null cloud with n > 0", who);
+    PCC_REQUIRE(scratch && index && depth, "%s: z-buffer, index and depth required", who);
+    PCC_REQUIRE(scratch_bytes >= pcc_render_scratch_bytes(a.H, a.W), "%s: scratch too small", who);
+    const int64_t npix = (int64_t)a.H * a.W;
+    hipStream_t st = as_stream(stream);
+    uint64_t* zbuf = reinterpret_cast<uint64_t*>(scratch);
+    hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
+    if (n > 0) hipLaunchKernelGGL(splat_kernel<View>, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
+    hipLaunchKernelGGL(buffers_kernel<View>, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix, index, depth);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+template <class View, int C>
+static void launch_sample(hipStream_t st, const View& a, const int32_t* coords, int64_t n, const uint64_t* zbuf, const int32_t* image,
+                          int32_t tolerance, int accumulate, int64_t* total, int32_t* count, int32_t* peak) {
+    hipLaunchKernelGGL((sample_kernel<View, C>), dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf, image, tolerance,
+                       accumulate, total, count, peak);
+}
+
+// What the two sample entries share: clear, splat, sample.
+template <class View>
+static int sample_back(const char* who, const View& a, const int32_t* coords, int64_t n, void* scratch, int64_t scratch_bytes,
+                       int32_t accumulate, const int32_t* image, int32_t channels, int32_t tolerance, int64_t* total, int32_t* count,
+                       int32_t* peak, void* stream) {
+    PCC_REQUIRE(channels >= 1 && channels <= PCC_SAMPLE_MAX_CHANNELS, "%s: channels must be 1 .. %d (got %d)", who,
+                PCC_SAMPLE_MAX_CHANNELS, channels);
+    PCC_REQUIRE(tolerance >= PCC_SAMPLE_OWN, "%s: tolerance is PCC_SAMPLE_OWN (-1) or a number of voxels >= 0 (got %d)", who, tolerance);
+    PCC_REQUIRE(image, "%s: image required", who);
+    PCC_REQUIRE(n == 0 || (coords && total && count && peak), "%s: null cloud or outputs with n > 0", who);
+    PCC_REQUIRE(scratch, "%s: z-buffer required", who);
+    PCC_REQUIRE(scratch_bytes >= pcc_render_scratch_bytes(a.H, a.W), "%s: scratch too small", who);
+    if (n == 0) return PCC_OK;                                // nothing to write, and the z-buffer is scratch: nothing to launch
+    const int64_t npix = (int64_t)a.H * a.W;
+    hipStream_t st = as_stream(stream);
+    uint64_t* zbuf = reinterpret_cast<uint64_t*>(scratch);
+    hipLaunchKernelGGL(render_clear_kernel, dim3(blocks_for(npix, 256)), dim3(256), 0, st, zbuf, npix);
+    hipLaunchKernelGGL(splat_kernel<View>, dim3(blocks_for(n, 256)), dim3(256), 0, st, coords, n, a, zbuf);
+    const int acc = accumulate != 0;
+    switch (channels) {
+        case 1: launch_sample<View, 1>(st, a, coords, n, zbuf, image, tolerance, acc, total, count, peak); break;
+        case 2: launch_sample<View, 2>(st, a, coords, n, zbuf, image, tolerance, acc, total, count, peak); break;
+        case 3: launch_sample<View, 3>(st, a, coords, n, zbuf, image, tolerance, acc, total, count, peak); break;
+        default: launch_sample<View, 4>(st, a, coords, n, zbuf, image, tolerance, acc, total, count, peak); break;
+    }
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
+// What the two image-compare entries share; mask == nullptr is the unmasked kernel.
+static int compare_images(const char* who, const uint8_t* ref, const uint8_t* img, const uint8_t* mask, int32_t H, int32_t W, void* scratch,
+                          int64_t scratch_bytes, double* out, void* stream) {
+    PCC_REQUIRE(H >= IC_WIN && W >= IC_WIN, "%s: images must be at least 7 x 7 (got %d x %d)", who, H, W);
+    PCC_REQUIRE(H <= RENDER_MAX_DIM && W <= RENDER_MAX_DIM, "%s: H and W must be at most %d (got %d x %d)", who, RENDER_MAX_DIM, H, W);
+    PCC_REQUIRE(ref && img && scratch && out, "%s: null pointer", who);
+    PCC_REQUIRE(scratch_bytes >= pcc_image_compare_scratch_bytes(H, W), "%s: scratch too small", who);
+    const int tiles_x = (W + IC_TILE - 1) / IC_TILE, tiles = tiles_x * ((H + IC_TILE - 1) / IC_TILE);
+    hipStream_t st = as_stream(stream);
+    double* partials = reinterpret_cast<double*>(scratch);
+    if (mask)
+        hipLaunchKernelGGL(image_compare_tile_kernel<true>, dim3(tiles), dim3(IC_THREADS), 0, st, ref, img, mask, H, W, tiles_x, partials);
+    else
+        hipLaunchKernelGGL(image_compare_tile_kernel<false>, dim3(tiles), dim3(IC_THREADS), 0, st, ref, img, mask, H, W, tiles_x, partials);
+    hipLaunchKernelGGL(image_compare_sum_kernel, dim3(1), dim3(64), 0, st, partials, tiles, out);
+    PCC_LAUNCH_CHECK();
+    return PCC_OK;
+}
+
 }  // namespace pcc
 
 using namespace pcc;
@@ -470,6 +631,39 @@ int pcc_camera_visibility(const int32_t* coords, int64_t n, const int32_t* pos_q
                      accumulate, behind, won, depth, stream);
 }
 
+int pcc_view_buffers(const int32_t* coords, int64_t n, const int32_t* right, const int32_t* up, const int32_t* front, int32_t u_min,
+                     int32_t v_max, int32_t ox, int32_t oy, int32_t scale, int32_t point_size, int32_t H, int32_t W, void* scratch,
+                     int64_t scratch_bytes, int32_t* index, int32_t* depth, void* stream) {
+    if (int rc = check_view("pcc_view_buffers", right, up, front, scale, point_size, H, W, n)) return rc;
+    return show_buffers("pcc_view_buffers", make_view(right, up, front, u_min, v_max, ox, oy, scale, point_size, H, W), coords, n, scratch,
+                        scratch_bytes, index, depth, stream);
+}
+
+int pcc_camera_buffers(const int32_t* coords, int64_t n, const int32_t* pos_q, const int32_t* axes_q, int32_t focal_q, int32_t near_q,
+                       int32_t H, int32_t W, int32_t ps_q, void* scratch, int64_t scratch_bytes, int32_t* index, int32_t* depth,
+                       void* stream) {
+    if (int rc = check_camera("pcc_camera_buffers", pos_q, axes_q, focal_q, near_q, ps_q, H, W, n)) return rc;
+    return show_buffers("pcc_camera_buffers", make_camera(pos_q, axes_q, focal_q, near_q, ps_q, H, W), coords, n, scratch, scratch_bytes,
+                        index, depth, stream);
+}
+
+int pcc_view_sample(const int32_t* coords, int64_t n, const int32_t* right, const int32_t* up, const int32_t* front, int32_t u_min,
+                    int32_t v_max, int32_t ox, int32_t oy, int32_t scale, int32_t point_size, int32_t H, int32_t W, void* scratch,
+                    int64_t scratch_bytes, int32_t accumulate, const int32_t* image, int32_t channels, int32_t tolerance, int64_t* total,
+                    int32_t* count, int32_t* peak, void* stream) {
+    if (int rc = check_view("pcc_view_sample", right, up, front, scale, point_size, H, W, n)) return rc;
+    return sample_back("pcc_view_sample", make_view(right, up, front, u_min, v_max, ox, oy, scale, point_size, H, W), coords, n, scratch,
+                       scratch_bytes, accumulate, image, channels, tolerance, total, count, peak, stream);
+}
+
+int pcc_camera_sample(const int32_t* coords, int64_t n, const int32_t* pos_q, const int32_t* axes_q, int32_t focal_q, int32_t near_q,
+                      int32_t H, int32_t W, int32_t ps_q, void* scratch, int64_t scratch_bytes, int32_t accumulate, const int32_t* image,
+                      int32_t channels, int32_t tolerance, int64_t* total, int32_t* count, int32_t* peak, void* stream) {
+    if (int rc = check_camera("pcc_camera_sample", pos_q, axes_q, focal_q, near_q, ps_q, H, W, n)) return rc;
+    return sample_back("pcc_camera_sample", make_camera(pos_q, axes_q, focal_q, near_q, ps_q, H, W), coords, n, scratch, scratch_bytes,
+                       accumulate, image, channels, tolerance, total, count, peak, stream);
+}
+
 int32_t pcc_image_compare_tile(void) { return IC_TILE; }
 
 int64_t pcc_image_compare_scratch_bytes(int32_t H, int32_t W) {
@@ -479,17 +673,13 @@ int64_t pcc_image_compare_scratch_bytes(int32_t H, int32_t W) {
 
 int pcc_image_compare(const uint8_t* ref, const uint8_t* img, int32_t H, int32_t W, void* scratch, int64_t scratch_bytes, double* out,
                       void* stream) {
-    PCC_REQUIRE(H >= IC_WIN && W >= IC_WIN, "pcc_image_compare: images must be at least 7 x 7 (got %d x %d)", H, W);
-    PCC_REQUIRE(H <= RENDER_MAX_DIM && W <= RENDER_MAX_DIM, "pcc_image_compare: H and W must be at most %d (got %d x %d)", RENDER_MAX_DIM, H, W);
-    PCC_REQUIRE(ref && img && scratch && out, "pcc_image_compare: null pointer");
-    PCC_REQUIRE(scratch_bytes >= pcc_image_compare_scratch_bytes(H, W), "pcc_image_compare: scratch too small");
-    const int tiles_x = (W + IC_TILE - 1) / IC_TILE, tiles = tiles_x * ((H + IC_TILE - 1) / IC_TILE);
-    hipStream_t st = as_stream(stream);
-    double* partials = reinterpret_cast<double*>(scratch);
-    hipLaunchKernelGGL(image_compare_tile_kernel, dim3(tiles), dim3(IC_THREADS), 0, st, ref, img, H, W, tiles_x, partials);
-    hipLaunchKernelGGL(image_compare_sum_kernel, dim3(1), dim3(64), 0, st, partials, tiles, out);
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    return compare_images("pcc_image_compare", ref, img, nullptr, H, W, scratch, scratch_bytes, out, stream);
+}
+
+int pcc_image_compare_masked(const uint8_t* ref, const uint8_t* img, const uint8_t* mask, int32_t H, int32_t W, void* scratch,
+                             int64_t scratch_bytes, double* out, void* stream) {
+    PCC_REQUIRE(mask, "pcc_image_compare_masked: mask required");
+    return compare_images("pcc_image_compare_masked", ref, img, mask, H, W, scratch, scratch_bytes, out, stream);
 }
 
 }  // extern "C"

@@ -20,7 +20,7 @@ from . import render
 from .io import write_png
 from .metrics import PointCloudMetric
 from .normals import estimate_normals
-from .q_map import facing_score, visibility_score
+from .q_map import box_image, facing_score, gaze_image, image_score, visibility_score
 from .sparse import SparseTensor
 
 
@@ -192,7 +192,7 @@ def _extent(points, axis):
 
 
 def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path, view="front", H=1024, W=512, gradient=None, roi=None,
-                            save_images=False, details=None, facing=None, visibility=None, camera=None, anchor=None):
+                            save_images=False, details=None, facing=None, visibility=None, camera=None, anchor=None, screen=None):
     """The three rows of evaluate_view_dep.py:139-301 for one frame -> {"uniform": row, "view": row, "roi": row}, each row
     {"bpp", "q_a", "q_g", "key", "psnr", "ssim"}.
 
@@ -231,7 +231,18 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
     the model's row with the same key; False: it is coded at ``qstep``), ``qstep`` (needed without ``match``), ``block_log2``, ``span``, ``colorspace``,
     ``contexts`` (anchor.compress's).  The rows carry ``"codec": "anchor"``, the ``qstep`` used, ``reached`` (False when even
     the coarsest step of the search is above the bytes to match), ``levels_bytes``, and q_a = q_g = None.  Images are saved as
-    ``anchor_<key>_<tag>.png``.  With ``anchor=None`` nothing changes."""
+    ``anchor_<key>_<tag>.png``.  With ``anchor=None`` nothing changes.
+
+    ``screen`` (a dict) appends a row "screen" after the others: quality by an IMAGE in the judged view — a detector's box, a
+    painted mask, a gaze point — carried back to the source's points by render.sample_views (render.sample_cameras with
+    ``camera``) through the judged view in the source's frame, and scored by q_map.image_score.  Its keys: exactly one of
+    ``image`` (an integer [H, W] array of the judged view's size, 255 = full quality), ``box`` (r0, r1, c0, c1: q_map.box_image)
+    and ``gaze`` (row, col, radius, falloff: q_map.gaze_image); ``tolerance`` (2: the pixels within two voxels of the point's
+    surface; None: only the pixels that show it), ``reduce`` ("max"), ``floor`` (0.0), ``point_size`` (as ``visibility``'s).
+    ``details["screen"]`` receives (total, count, peak, score), so the row's own (cloud, image) pair goes to
+    ``details["screen_row"]``.  Every row, anchor rows included, then also carries ``psnr_roi``
+    and ``ssim_roi``: render.view_metrics with ``mask = image > 0``, so that the uniform and plane-ROI rows can be compared with
+    the screen row INSIDE the region.  With ``screen=None`` nothing changes."""
     if anchor is not None:
         unknown = set(anchor) - {"qstep", "match", "block_log2", "span", "colorspace", "contexts"}
         if unknown:
@@ -291,10 +302,45 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
         maps["visible"] = vis_score.to(torch.float)
         if details is not None:
             details["visibility"] = (behind, vis_score)
+    roi_mask = None
+    if screen is not None:
+        unknown = set(screen) - {"image", "box", "gaze", "tolerance", "reduce", "floor", "point_size"}
+        if unknown:
+            raise ValueError("screen: unknown keys %s" % sorted(unknown))
+        if sum(k in screen for k in ("image", "box", "gaze")) != 1:
+            raise ValueError("screen: give exactly one of image, box and gaze")
+        s_h, s_w = (camera.H, camera.W) if camera is not None else (int(H), int(W))
+        if "box" in screen:
+            s_img = box_image(s_h, s_w, screen["box"])
+        elif "gaze" in screen:
+            g_row, g_col, g_radius, g_falloff = screen["gaze"]
+            s_img = gaze_image(s_h, s_w, (g_row, g_col), g_radius, g_falloff)
+        else:
+            s_img = screen["image"]
+        s_img = s_img if torch.is_tensor(s_img) else torch.as_tensor(np.asarray(s_img))
+        if s_img.dim() != 2 or tuple(s_img.shape) != (s_h, s_w):
+            raise ValueError("screen: the image is [H, W] of the judged view's size %d x %d, got %s" % (s_h, s_w, tuple(s_img.shape)))
+        size = screen.get("point_size")
+        if camera is None:
+            sampled = render.sample_views(points, [view], [s_img], H, W, point_size=size, tolerance=screen.get("tolerance", 2), device=device)
+        else:
+            sampled = render.sample_cameras(points, [camera], [s_img], point_size=1.0 if size is None else size,
+                                            tolerance=screen.get("tolerance", 2), device=device)
+        screen_score = image_score(*sampled, reduce=screen.get("reduce", "max"), floor=screen.get("floor", 0.0))
+        maps["screen"] = screen_score.to(torch.float)
+        roi_mask = (s_img > 0).to(device)
+        if details is not None:
+            details["screen"] = sampled + (screen_score,)
     img_dir = os.path.join(base_path, experiment, "renders_view")
     if save_images:
         os.makedirs(img_dir, exist_ok=True)
     rows, frame, ref_img = {}, None, None
+
+    def judge_region(row, img):
+        if roi_mask is not None:
+            m_roi = render.view_metrics(ref_img, img, mask=roi_mask)
+            row["psnr_roi"], row["ssim_roi"] = m_roi["psnr"], m_roi["ssim"]
+
     for key, score in maps.items():
         qa = q_a if score is None else (float(q_a) * score).reshape(-1, 1)
         qg = q_g if score is None else (float(q_g) * score).reshape(-1, 1)
@@ -314,10 +360,11 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
         img = draw(rec)
         m = render.view_metrics(ref_img, img)
         rows[key] = {"bpp": bpp, "q_a": q_a, "q_g": q_g, "key": key, "psnr": m["psnr"], "ssim": m["ssim"]}
+        judge_region(rows[key], img)
         if save_images:
             write_png(os.path.join(img_dir, "%s_a%s_g%s_%s.png" % (key, str(q_a), str(q_g), tag)), img)
         if details is not None:
-            details[key] = (rec, img)
+            details["screen_row" if key == "screen" else key] = (rec, img)      # details["screen"] holds the sampled arrays
     if anchor is not None:
         from . import anchor as anchor_codec
         match, qstep = anchor.get("match", True), anchor.get("qstep")
@@ -335,6 +382,7 @@ def evaluate_view_dependent(experiment, model, data, q_a, q_g, device, base_path
             name = "anchor_" + key
             rows[name] = {"bpp": len(stream) * 8 / n, "q_a": None, "q_g": None, "key": name, "psnr": m["psnr"], "ssim": m["ssim"],
                           "codec": "anchor", "qstep": step, "reached": reached, "levels_bytes": _levels_bytes(stream)}
+            judge_region(rows[name], img)
             if save_images:
                 write_png(os.path.join(img_dir, "%s_%s.png" % (name, tag)), img)
             if details is not None:

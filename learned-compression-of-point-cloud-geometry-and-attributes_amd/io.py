@@ -9,7 +9,8 @@ A cloud is a float32 ``[N, 6]`` array: voxel coordinates and rgb in [0, 1] — t
 ``ColorModel.compress`` takes (model/model.py:95-123).
 
 ``write_png`` writes the rendered views of the view-dependent evaluation (evaluate_view_dep.py:346,
-``capture_screen_image``) with the standard library alone: no imaging package is assumed.
+``capture_screen_image``) with the standard library alone: no imaging package is assumed.  ``read_png`` reads 8-bit
+non-interlaced PNGs the same way: the painted masks and saliency maps of the screen-space quality maps.
 """
 import struct
 import zlib
@@ -130,3 +131,86 @@ def write_png(path, img):
     with open(path, "wb") as f:
         f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
                 + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
+_PNG_CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}          # colour type -> samples per pixel: grey, RGB, grey + alpha, RGBA
+
+
+def read_png(path):
+    """An 8-bit non-interlaced PNG (a path or its bytes) -> uint8 [H, W] for grey, [H, W, 2] for grey + alpha, [H, W, 3] for RGB,
+    [H, W, 4] for RGBA: what a painted mask or a saliency map comes as (tools/view_dep.py --screen-mask), and what ``write_png``
+    writes.  All five scanline filters; every chunk's CRC is checked; ancillary chunks are skipped.  ValueError for anything
+    else: a palette, another bit depth, interlacing, a damaged file."""
+    if isinstance(path, (bytes, bytearray, memoryview)):
+        raw = bytes(path)
+    else:
+        with open(path, "rb") as f:
+            raw = f.read()
+    if raw[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError("read_png: not a PNG (bad signature)")
+    pos, head, data, ended = 8, None, [], False
+    while pos < len(raw) and not ended:
+        if pos + 12 > len(raw):
+            raise ValueError("read_png: truncated chunk")
+        n, tag = struct.unpack(">I4s", raw[pos:pos + 8])
+        if pos + 12 + n > len(raw):
+            raise ValueError("read_png: truncated chunk %r" % tag)
+        body = raw[pos + 8:pos + 8 + n]
+        if struct.unpack(">I", raw[pos + 8 + n:pos + 12 + n])[0] != zlib.crc32(tag + body) & 0xFFFFFFFF:
+            raise ValueError("read_png: bad CRC in chunk %r" % tag)
+        if head is None and tag != b"IHDR":
+            raise ValueError("read_png: the first chunk is not IHDR")
+        if tag == b"IHDR":
+            if head is not None or n != 13:
+                raise ValueError("read_png: bad IHDR")
+            head = struct.unpack(">IIBBBBB", body)
+        elif tag == b"IDAT":
+            data.append(body)
+        elif tag == b"IEND":
+            ended = True
+        elif not tag[0] & 0x20:                                # a critical chunk this reader does not know (PLTE among them)
+            raise ValueError("read_png: unsupported critical chunk %r" % tag)
+        pos += 12 + n
+    if head is None or not ended:
+        raise ValueError("read_png: no IHDR or no IEND")
+    w, h, depth, colour, comp, filt, lace = head
+    if depth != 8 or colour not in _PNG_CHANNELS or comp != 0 or filt != 0 or lace != 0 or w < 1 or h < 1:
+        raise ValueError("read_png: only 8-bit grey, grey + alpha, RGB and RGBA, non-interlaced (got depth %d, colour type %d, "
+                         "interlace %d)" % (depth, colour, lace))
+    bpp = _PNG_CHANNELS[colour]
+    stride = w * bpp
+    try:
+        flat = zlib.decompress(b"".join(data))
+    except zlib.error as e:
+        raise ValueError("read_png: %s" % e) from None
+    if len(flat) != h * (1 + stride):
+        raise ValueError("read_png: %d bytes of image data for %d x %d x %d" % (len(flat), h, w, bpp))
+    lines = np.frombuffer(flat, dtype=np.uint8).reshape(h, 1 + stride)
+    out = np.zeros((h, stride), dtype=np.uint8)
+    prev = np.zeros(stride, dtype=np.int64)
+    for y in range(h):
+        kind, line = int(lines[y, 0]), lines[y, 1:].astype(np.int64)
+        if kind == 0:
+            cur = line
+        elif kind == 2:                                        # Up
+            cur = (line + prev) & 255
+        elif kind in (1, 3, 4):                                # Sub, Average, Paeth: each byte needs the one bpp to its left
+            cur = np.zeros(stride, dtype=np.int64)
+            for x in range(stride):
+                a = int(cur[x - bpp]) if x >= bpp else 0
+                b = int(prev[x])
+                if kind == 1:
+                    pred = a
+                elif kind == 3:
+                    pred = (a + b) >> 1
+                else:
+                    c = int(prev[x - bpp]) if x >= bpp else 0
+                    p = a + b - c
+                    pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
+                    pred = a if pa <= pb and pa <= pc else (b if pb <= pc else c)
+                cur[x] = (int(line[x]) + pred) & 255
+        else:
+            raise ValueError("read_png: unknown filter type %d on line %d" % (kind, y))
+        out[y] = cur
+        prev = cur
+    return out.reshape(h, w) if bpp == 1 else out.reshape(h, w, bpp)

@@ -9,7 +9,8 @@ seeded run draws the same maps — and returns it together with the lambda map u
 evaluation scripts (utils.py:436-445, evaluate_view_dep.py:207-260); ``facing_map`` is the second half of the view-dependent
 experiment (evaluate_view_dep.py:354-376): quality by the angle between a point's normal and the viewing ray; ``visibility_map`` goes one step further and scores a point
 by what the judged views can show at all (render.visibility: how far it lies behind the z-buffer front); ``distance_map`` scores
-it by how large a camera at a position sees it (render.camera_visibility's depth).  Elementwise work
+it by how large a camera at a position sees it (render.camera_visibility's depth); ``image_map`` scores it by an IMAGE in the
+judged view (a box, a mask, a gaze point: ``box_image`` / ``gaze_image``) that render.sample_views carried back to the points.  Elementwise work
 on [N, 2] tensors; plain torch.
 """
 import math
@@ -143,6 +144,84 @@ def distance_map(coords_map, depth, focal, q_g, q_a, full=1.0, floor=0.0):
         raise ValueError("distance map: %d scores for %d coordinates" % (score.shape[0], coords_map.n))
     score = score.to(coords_map.device)
     return SparseTensor(torch.stack([float(q_g) * score, float(q_a) * score], dim=1).to(torch.float32).contiguous(), coordinate_map=coords_map)
+
+
+def image_score(total, count, peak, reduce="max", channel=0, scale=255, floor=0.0):
+    """float64 [N]: floor + (1 - floor) * clip(v / scale, 0, 1) from what render.sample_views / sample_cameras bring back from an
+    image (``total`` int64 [N, C], ``count`` int32 [N], ``peak`` int32 [N, C]): v = peak[:, channel] for ``reduce="max"`` (the
+    brightest pixel that looks at the point), total[:, channel] / count for ``reduce="mean"``.  A point no pixel counted for
+    (count == 0) scores ``floor``.  ``scale`` is the image value that means full quality (255 for a byte image).  Float64
+    arithmetic on the integer inputs."""
+    if reduce not in ("max", "mean"):
+        raise ValueError("image score: reduce is 'max' or 'mean' (got %r)" % (reduce,))
+    scale, floor = float(scale), float(floor)
+    if not (scale > 0 and math.isfinite(scale)):
+        raise ValueError("image score: scale is positive (got %r)" % scale)
+    if not 0.0 <= floor <= 1.0:
+        raise ValueError("image score: floor is in [0, 1] (got %r)" % floor)
+    total, count, peak = torch.as_tensor(total), torch.as_tensor(count), torch.as_tensor(peak)
+    if any(t.is_floating_point() or t.is_complex() or t.dtype == torch.bool for t in (total, count, peak)):
+        raise ValueError("image score: total, count and peak are integer tensors (render.sample_views' results)")
+    if count.dim() != 1 or total.dim() != 2 or peak.shape != total.shape or total.shape[0] != count.shape[0]:
+        raise ValueError("image score: total and peak are [N, C], count is [N]")
+    if not 0 <= int(channel) < total.shape[1]:
+        raise ValueError("image score: channel %r of %d" % (channel, total.shape[1]))
+    seen = count > 0
+    if reduce == "max":
+        v = peak[:, int(channel)].to(torch.float64)
+    else:
+        v = total[:, int(channel)].to(torch.float64) / count.clamp_min(1).to(torch.float64)
+    # a tensor divisor: dividing a GPU tensor by a Python number multiplies by its reciprocal, which is not the rounded quotient
+    w = torch.clamp(v / torch.full_like(v, scale), min=0.0, max=1.0)
+    w = torch.where(seen, w, torch.zeros_like(w))
+    return floor + (1.0 - floor) * w
+
+
+def image_map(coords_map, total, count, peak, q_g, q_a, reduce="max", channel=0, scale=255, floor=0.0):
+    """a screen-space quality map: score = image_score(total, count, peak, ...), channels [q_g * score, q_a * score] (float64
+    products, cast to float32 — as visibility_map).  The three tensors must be in the row order of ``coords_map.coords``:
+    ``total, count, peak = render.sample_views(coords_map.coords[:, 1:4], views, images, H, W, tolerance=2)``."""
+    score = image_score(total, count, peak, reduce, channel, scale, floor)
+    if score.shape[0] != coords_map.n:
+        raise ValueError("image map: %d scores for %d coordinates" % (score.shape[0], coords_map.n))
+    score = score.to(coords_map.device)
+    return SparseTensor(torch.stack([float(q_g) * score, float(q_a) * score], dim=1).to(torch.float32).contiguous(), coordinate_map=coords_map)
+
+
+def _image_shape(H, W):
+    if not (int(H) == H and int(W) == W and int(H) >= 1 and int(W) >= 1):
+        raise ValueError("an image is H x W pixels, both at least 1 (got %r x %r)" % (H, W))
+    return int(H), int(W)
+
+
+def box_image(H, W, box):
+    """uint8 [H, W] numpy array: 255 in rows r0 .. r1 - 1 and columns c0 .. c1 - 1 of ``box = (r0, r1, c0, c1)`` (clipped to the
+    image), 0 elsewhere — a detector's box as an image for render.sample_views"""
+    import numpy as np
+    H, W = _image_shape(H, W)
+    r0, r1, c0, c1 = (int(v) for v in box)
+    img = np.zeros((H, W), dtype=np.uint8)
+    img[max(r0, 0):max(r1, 0), max(c0, 0):max(c1, 0)] = 255
+    return img
+
+
+def gaze_image(H, W, gaze, radius, falloff):
+    """uint8 [H, W] numpy array: 255 within ``radius`` pixels of the gaze point ``gaze = (row, col)``, running linearly to 0 over
+    ``falloff`` further pixels: rint(255 * clip(1 - (dist - radius) / falloff, 0, 1)) in float64, dist the Euclidean distance of
+    the pixel's (row, col) from the gaze point; with falloff == 0 a hard disc"""
+    import numpy as np
+    H, W = _image_shape(H, W)
+    row, col = (float(v) for v in gaze)
+    radius, falloff = float(radius), float(falloff)
+    if not (radius >= 0 and falloff >= 0 and math.isfinite(radius) and math.isfinite(falloff)):
+        raise ValueError("gaze image: radius and falloff are non-negative (got %r, %r)" % (radius, falloff))
+    rr, cc = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    dist = np.sqrt((rr - row) * (rr - row) + (cc - col) * (cc - col))
+    if falloff > 0:
+        w = np.clip(1.0 - (dist - radius) / falloff, 0.0, 1.0)
+    else:
+        w = (dist <= radius).astype(np.float64)
+    return np.rint(255.0 * w).astype(np.uint8)
 
 
 class Q_Map:

@@ -22,6 +22,11 @@ behind the z-buffer front of the given views and how many pixels show it — wha
 camera quantised to integers on the host, a perspective projection in int64 on the device (``pcc_render_camera``,
 ``pcc_camera_visibility``), and per point also its depth, which q_map.distance_map turns into a quality map.
 
+``view_buffers`` / ``camera_buffers`` return the z-buffer itself (the row and the depth every pixel shows), and ``sample_views``
+/ ``sample_cameras`` carry an IMAGE back to the points (``pcc_view_sample``, ``pcc_camera_sample``): per point the sum, the
+number and the maximum of an integer image over the pixels that look at it — what q_map.image_map builds a screen-space
+quality map from (a detector's box, a painted mask, a gaze point).
+
 ``view_metrics`` restates scikit-image's formulas in float64 (``pcc_image_compare``).  scikit-image is no dependency of
 this project and was not at hand: the ``yuv_from_rgb`` coefficients, the SSIM constants (K1 = 0.01, K2 = 0.03, 7 x 7
 uniform window, sample covariance, crop of 3) and the data-range rule of ``peak_signal_noise_ratio`` are recalled from its
@@ -42,6 +47,9 @@ VIEWS_MVUB = {"front": ((0, -1, 0), (0, 0, 1)), "side": ((-1, 0, 0), (0, 0, 1))}
 
 COORD_LIMIT = _lib.PCC.COORD_LIMIT
 OFFSCREEN = _lib.PCC.VIS_OFFSCREEN             # ``visibility``'s ``behind`` of a point no pixel of whose splat is inside the image
+SAMPLE_OWN = _lib.PCC.SAMPLE_OWN               # ``sample_views``' tolerance that means "the pixels that show the point"
+SAMPLE_NONE = _lib.PCC.SAMPLE_NONE             # ``peak`` of a point no pixel counted for
+SAMPLE_MAX_CHANNELS = _lib.PCC.SAMPLE_MAX_CHANNELS
 MAX_DIM = 8192                                 # the largest image side the renderer takes (csrc/render.hip, RENDER_MAX_DIM)
 
 
@@ -440,6 +448,179 @@ def camera_visibility(cloud, cameras, point_size=1.0, device=None):
         return _input_order(perm, behind, won, depth)
 
 
+def _frames(frames, n_views):
+    if frames is not None:
+        if not isinstance(frames, (list, tuple)) or len(frames) != n_views:
+            raise ValueError("frames is None or one view_frame result per view (%d views)" % n_views)
+        if any(not isinstance(fr, (list, tuple)) or len(fr) != 7 for fr in frames):
+            raise ValueError("a frame is a view_frame result: (u_min, u_max, v_min, v_max, scale, ox, oy)")
+
+
+def _cameras(who, cameras):
+    if isinstance(cameras, Camera) or not isinstance(cameras, (list, tuple)):
+        raise ValueError("cameras is a list of render.Camera, got %r" % (cameras,))
+    if len(cameras) == 0:
+        raise ValueError("cameras is empty: %s needs at least one camera" % who)
+    if any(not isinstance(c, Camera) for c in cameras):
+        raise ValueError("cameras is a list of render.Camera, got %r" % (cameras,))
+
+
+def _row_index(index, perm):
+    """a plane of canonically sorted row numbers (-1: background) -> the same in the input's row numbers"""
+    if perm is None:
+        return index
+    shown = index >= 0
+    return torch.where(shown, perm.to(torch.int32)[index.clamp_min(0).long()], index)
+
+
+def view_buffers(cloud, front, up, H, W, frame=None, point_size=None, device=None):
+    """The z-buffer ``render_view`` resolves its image from -> (index, depth): int32 [H, W] tensors on the GPU
+    (``pcc_view_buffers``).  ``index`` is the row of ``cloud`` (in the INPUT's row order) every pixel shows under the renderer's
+    full winner rule, -1 for background: ``render_view``'s image is ``rgb8[index]`` with the background where index < 0.
+    ``depth`` is d = front . p of that row, ``OFFSCREEN`` for background.  The arguments are ``render_view``'s; colours are not
+    needed.  An empty cloud gives all background."""
+    r, u, f = view_axes(front, up)
+    cloud, xyz, n, dev = _cloud("view_buffers", cloud, device)
+    H, W = _image_size(H, W)
+    if frame is None:
+        frame = view_frame(xyz, f, u, H, W)
+    u_min, _, _, v_max, scale, ox, oy = (int(v) for v in frame)
+    point_size = scale if point_size is None else int(point_size)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        coords, _, perm = _sorted_rows(L, cloud, xyz, dev, colours=False)
+        zbuf, zbytes = _zbuffer(L, dev, [(H, W)])
+        index, depth = (torch.empty((H, W), dtype=torch.int32, device=dev) for _ in range(2))
+        axes = [np.asarray(a, dtype=np.int32) for a in (r, u, f)]
+        check(L.pcc_view_buffers(ptr(coords) if n else None, n, ptr(axes[0]), ptr(axes[1]), ptr(axes[2]), u_min, v_max, ox, oy, scale,
+                                 point_size, H, W, ptr(zbuf), zbytes, ptr(index), ptr(depth), _lib.stream()))
+        return _row_index(index, perm), depth
+
+
+def camera_buffers(cloud, camera, point_size=1.0, device=None):
+    """``view_buffers`` for a ``Camera`` -> (index, depth): int32 [H, W] (the camera's size) on the GPU (``pcc_camera_buffers``).
+    ``depth`` is the shown row's depth key (1/256 voxel along the viewing direction), ``OFFSCREEN`` for background."""
+    if not isinstance(camera, Camera):
+        raise ValueError("camera_buffers: camera is a render.Camera, got %r" % (camera,))
+    ps_q = _ps_q(point_size)
+    cloud, xyz, n, dev = _cloud("camera_buffers", cloud, device)
+    pos, axes, q = _camera_args(camera)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        coords, _, perm = _sorted_rows(L, cloud, xyz, dev, colours=False)
+        zbuf, zbytes = _zbuffer(L, dev, [(q.H, q.W)])
+        index, depth = (torch.empty((q.H, q.W), dtype=torch.int32, device=dev) for _ in range(2))
+        check(L.pcc_camera_buffers(ptr(coords) if n else None, n, ptr(pos), ptr(axes), q.focal_q, q.near_q, q.H, q.W, ps_q, ptr(zbuf),
+                                   zbytes, ptr(index), ptr(depth), _lib.stream()))
+        return _row_index(index, perm), depth
+
+
+def _sample_images(who, images, sizes):
+    """one integer / bool [H, W] or [H, W, C] array or tensor per view -> ([H, W, C] int32 tensors (on their own devices), C);
+    ValueError for anything else, before the GPU is touched"""
+    if torch.is_tensor(images) or isinstance(images, np.ndarray) or not isinstance(images, (list, tuple)) or len(images) != len(sizes):
+        raise ValueError("%s: images is a list of one image per view (%d views)" % (who, len(sizes)))
+    out, channels = [], None
+    for image, (H, W) in zip(images, sizes):
+        t = image if torch.is_tensor(image) else torch.as_tensor(np.asarray(image))
+        if t.is_floating_point() or t.is_complex():
+            raise ValueError("%s: an image holds integers or bools (the operator is exact: quantise a float image first), got %s" % (who, t.dtype))
+        if t.dim() == 2:
+            t = t.unsqueeze(2)
+        if t.dim() != 3 or (int(t.shape[0]), int(t.shape[1])) != (H, W):
+            raise ValueError("%s: an image is [H, W] or [H, W, C] of its view's size %d x %d, got %s" % (who, H, W, tuple(image.shape)))
+        if not 1 <= int(t.shape[2]) <= SAMPLE_MAX_CHANNELS:
+            raise ValueError("%s: an image has 1 .. %d channels, got %d" % (who, SAMPLE_MAX_CHANNELS, int(t.shape[2])))
+        if channels is not None and int(t.shape[2]) != channels:
+            raise ValueError("%s: every image has the same number of channels" % who)
+        channels = int(t.shape[2])
+        narrow = (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32)
+        if t.dtype not in narrow and t.numel() and not (int(t.min()) >= -0x80000000 and int(t.max()) <= 0x7FFFFFFF):
+            raise ValueError("%s: image values must fit int32" % who)
+        out.append(t.to(torch.int32))
+    return out, channels
+
+
+def _tolerance(who, tolerance):
+    if tolerance is None:
+        return SAMPLE_OWN
+    try:
+        t = int(tolerance)
+        ok = t == tolerance and 0 <= t <= 0x7FFFFFFF
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("%s: tolerance is None (the pixels that show the point) or a whole number of voxels >= 0, got %r" % (who, tolerance))
+    return t
+
+
+def _sample_outputs(n, channels, dev):
+    return (torch.zeros((n, channels), dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+            torch.full((n, channels), SAMPLE_NONE, dtype=torch.int32, device=dev))
+
+
+def sample_views(cloud, views, images, H, W, frames=None, point_size=None, tolerance=None, device=None):
+    """Carry ``images`` back to the points through ``views`` -> (total, count, peak): int64 [N, C], int32 [N], int32 [N, C]
+    tensors on the GPU in the INPUT's row order (csrc/render.hip, ``pcc_view_sample``).
+
+    For one view, with the geometry, clipping and winner rule of ``render_view`` at H x W: a pixel of point i's splat COUNTS for
+    the point when it shows the point (``tolerance=None``: ``count`` is ``visibility``'s ``won``), or when the z-buffer front of the
+    pixel is at most ``tolerance`` voxels in front of the point (``tolerance >= 0``: the quantity whose minimum is ``behind``, so
+    count > 0 exactly where behind <= tolerance).  ``total`` is the sum of the image over the counted pixels, ``count`` their
+    number, ``peak`` the maximum (``SAMPLE_NONE`` when nothing counted).  Over several views: sum, sum, maximum.  All integer and
+    bitwise reproducible; the operator is exact, so callers quantise (a float image is a ValueError).
+
+    ``images``: one integer or bool array or tensor per view, [H, W] or [H, W, C] with C <= 4.  ``views``, ``frames`` and
+    ``point_size`` as in ``visibility``.  No sub-pixel sampling: a point reads whole pixels of its own splat."""
+    axes = _views(views)
+    _frames(frames, len(axes))
+    H, W = _image_size(H, W)
+    tol = _tolerance("sample_views", tolerance)
+    images, channels = _sample_images("sample_views", images, [(H, W)] * len(axes))
+    cloud, xyz, n, dev = _cloud("sample_views", cloud, device)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        total, count, peak = _sample_outputs(n, channels, dev)
+        if n == 0:
+            return total, count, peak
+        xyz = xyz.to(dev)
+        coords, _, perm = _sorted_rows(L, cloud, xyz, dev, colours=False)
+        zbuf, zbytes = _zbuffer(L, dev, [(H, W)])
+        for k, (r, u, f) in enumerate(axes):
+            frame = view_frame(xyz, f, u, H, W) if frames is None else frames[k]
+            u_min, _, _, v_max, scale, ox, oy = (int(v) for v in frame)
+            size = scale if point_size is None else int(point_size)
+            vecs = [np.asarray(a, dtype=np.int32) for a in (r, u, f)]
+            image = images[k].to(dev).contiguous()
+            check(L.pcc_view_sample(ptr(coords), n, ptr(vecs[0]), ptr(vecs[1]), ptr(vecs[2]), u_min, v_max, ox, oy, scale, size, H, W,
+                                    ptr(zbuf), zbytes, int(k > 0), ptr(image), channels, tol, ptr(total), ptr(count), ptr(peak),
+                                    _lib.stream()))
+        return _input_order(perm, total, count, peak)
+
+
+def sample_cameras(cloud, cameras, images, point_size=1.0, tolerance=None, device=None):
+    """``sample_views`` for a non-empty list of ``Camera`` (``pcc_camera_sample``): every image has its camera's size, and
+    ``tolerance`` counts whole voxels of depth as ``camera_visibility``'s ``behind`` does."""
+    _cameras("sample_cameras", cameras)
+    ps_q = _ps_q(point_size)
+    tol = _tolerance("sample_cameras", tolerance)
+    images, channels = _sample_images("sample_cameras", images, [(c.H, c.W) for c in cameras])
+    cloud, xyz, n, dev = _cloud("sample_cameras", cloud, device)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        total, count, peak = _sample_outputs(n, channels, dev)
+        if n == 0:
+            return total, count, peak
+        coords, _, perm = _sorted_rows(L, cloud, xyz, dev, colours=False)
+        zbuf, zbytes = _zbuffer(L, dev, [(c.H, c.W) for c in cameras])
+        for k, camera in enumerate(cameras):
+            pos, axes, q = _camera_args(camera)
+            image = images[k].to(dev).contiguous()
+            check(L.pcc_camera_sample(ptr(coords), n, ptr(pos), ptr(axes), q.focal_q, q.near_q, q.H, q.W, ps_q, ptr(zbuf), zbytes,
+                                      int(k > 0), ptr(image), channels, tol, ptr(total), ptr(count), ptr(peak), _lib.stream()))
+        return _input_order(perm, total, count, peak)
+
+
 def data_range_of(ref_min):
     """scikit-image's rule for float images when ``peak_signal_noise_ratio`` is given no data_range: 1 if the reference
     image's smallest value is >= 0, else 2 (the range of [-1, 1]) — what evaluate_view_dep.py:203 gets, since U and V are
@@ -447,10 +628,20 @@ def data_range_of(ref_min):
     return 1.0 if ref_min >= 0 else 2.0
 
 
-def image_compare(ref_img, img):
+def _mask(who, mask, H, W, dev):
+    """a bool or integer [H, W] array or tensor -> uint8 [H, W] on ``dev``, 1 where it is nonzero"""
+    t = mask if torch.is_tensor(mask) else torch.as_tensor(np.asarray(mask))
+    if t.dim() != 2 or (int(t.shape[0]), int(t.shape[1])) != (H, W):
+        raise ValueError("%s: the mask is [H, W] of the images' size %d x %d, got %s" % (who, H, W, tuple(t.shape)))
+    return (t.to(dev) != 0).to(torch.uint8).contiguous()
+
+
+def image_compare(ref_img, img, mask=None):
     """The raw sums of ``pcc_image_compare`` for two uint8 [H, W, 3] GPU images -> eight floats: per-channel (Y, U, V) sums
     of squared differences, per-channel sums of the SSIM map over its (H - 6) x (W - 6) crop, smallest and largest YUV value
-    of ``ref_img``.  Bitwise reproducible."""
+    of ``ref_img``.  Bitwise reproducible.  ``mask`` ([H, W], nonzero = inside; ``pcc_image_compare_masked``): the squared
+    differences of the masked pixels only and the SSIM values of the windows whose centre pixel is masked; the last two stay
+    over the whole image."""
     L = _lib.lib()
     if not (torch.is_tensor(ref_img) and torch.is_tensor(img)):
         raise ValueError("image_compare: images are uint8 [H, W, 3] tensors on the GPU")
@@ -465,27 +656,44 @@ def image_compare(ref_img, img):
         nbytes = L.pcc_image_compare_scratch_bytes(H, W)
         scratch = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
         out = torch.empty(8, dtype=torch.float64, device=dev)
-        check(L.pcc_image_compare(ptr(a), ptr(b), H, W, ptr(scratch), nbytes, ptr(out), _lib.stream()))
+        if mask is None:
+            check(L.pcc_image_compare(ptr(a), ptr(b), H, W, ptr(scratch), nbytes, ptr(out), _lib.stream()))
+        else:
+            m = _mask("image_compare", mask, H, W, dev)
+            check(L.pcc_image_compare_masked(ptr(a), ptr(b), ptr(m), H, W, ptr(scratch), nbytes, ptr(out), _lib.stream()))
         return out.tolist()
 
 
-def metrics_from_sums(sums, H, W, data_range=None):
-    """the numbers of ``view_metrics`` from the eight raw sums of an H x W pair"""
-    n = float(H * W)
-    y_mse, u_mse, v_mse = (s / n for s in sums[0:3])
-    mse = (sums[0] + sums[1] + sums[2]) / (3.0 * n)
+def metrics_from_sums(sums, H, W, data_range=None, pixels=None, windows=None):
+    """the numbers of ``view_metrics`` from the eight raw sums of an H x W pair; ``pixels`` / ``windows``: the numbers of masked
+    pixels and masked windows the sums ran over (None: all of them).  A mean over an empty set is nan."""
+    n = float(H * W) if pixels is None else float(pixels)
+    nan = float("nan")
+    y_mse, u_mse, v_mse = ((s / n if n > 0 else nan) for s in sums[0:3])
+    mse = (sums[0] + sums[1] + sums[2]) / (3.0 * n) if n > 0 else nan
     if data_range is None:
         data_range = data_range_of(sums[6])
-    crop = float((H - 6) * (W - 6))
-    ssim = (sums[3] / crop + sums[4] / crop + sums[5] / crop) / 3.0
-    psnr = math.inf if mse <= 0 else 10.0 * math.log10(float(data_range) ** 2 / mse)
+    crop = float((H - 6) * (W - 6)) if windows is None else float(windows)
+    ssim = (sums[3] / crop + sums[4] / crop + sums[5] / crop) / 3.0 if crop > 0 else nan
+    if math.isnan(mse):
+        psnr = nan
+    else:
+        psnr = math.inf if mse <= 0 else 10.0 * math.log10(float(data_range) ** 2 / mse)
     return {"psnr": psnr, "ssim": ssim, "y_mse": y_mse, "u_mse": u_mse, "v_mse": v_mse}
 
 
-def view_metrics(ref_img, img, data_range=None):
+def view_metrics(ref_img, img, data_range=None, mask=None):
     """PSNR and SSIM of a rendered view against the reference view, in YUV as evaluate_view_dep.py:196-204 takes them ->
     {"psnr", "ssim", "y_mse", "u_mse", "v_mse"}.  PSNR = 10 log10(data_range^2 / mse), mse over all 3 H W values (inf at 0);
     ``data_range=None`` follows ``data_range_of``.  SSIM is the mean of the three channels' mean SSIM
-    (structural_similarity(channel_axis=2, data_range=1.0), 7 x 7 uniform window)."""
-    sums = image_compare(ref_img, img)
-    return metrics_from_sums(sums, int(ref_img.shape[0]), int(ref_img.shape[1]), data_range)
+    (structural_similarity(channel_axis=2, data_range=1.0), 7 x 7 uniform window).
+
+    ``mask`` ([H, W], nonzero = inside) restricts the judgement to a region: the mean squared errors run over the masked pixels,
+    the SSIM over the windows of its crop whose centre pixel is masked; the data-range rule still reads the whole reference.  A
+    metric over an empty set (no masked pixel, or none away from the 3-pixel border) is nan.  ``mask=None`` is the whole image."""
+    H, W = int(ref_img.shape[0]), int(ref_img.shape[1])
+    if mask is None:
+        return metrics_from_sums(image_compare(ref_img, img), H, W, data_range)
+    sums = image_compare(ref_img, img, mask)
+    m = _mask("view_metrics", mask, H, W, ref_img.device)
+    return metrics_from_sums(sums, H, W, data_range, pixels=int(m.sum()), windows=int(m[3:H - 3, 3:W - 3].sum()))

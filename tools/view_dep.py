@@ -20,7 +20,11 @@ usage: view_dep.py [config1 | config2 | frame.ply] [--out DIR] [--view front|sid
                    defaults to the middle of the frame's bounding box; --visibility then asks render.camera_visibility of this camera)
                    [--anchor [--anchor-qstep Q] [--anchor-span 24]]     (one row "anchor_<key>" per row: the octree + RAHT anchor
                    codec with the row's map as region-wise quantisation, searched to the bytes of the model's row, or coded at
-                   --anchor-qstep (in 1/255 units) when that is given; the CSV gains the columns codec and qstep)"""
+                   --anchor-qstep (in 1/255 units) when that is given; the CSV gains the columns codec and qstep)
+                   [--screen-box R0,R1,C0,C1 | --screen-mask FILE.png | --gaze ROW,COL,RADIUS,FALLOFF] [--screen-tolerance 2]     (a row
+                   "screen": quality by an image in the judged view — a box, a painted mask (an 8-bit PNG of the view's size, its first
+                   channel), a gaze point — carried back to the points, render.sample_views; the CSV gains the columns psnr_roi and
+                   ssim_roi, every row judged inside the region; --screen-tolerance -1 samples only the pixels that show a point)"""
 import argparse
 import csv
 import json
@@ -41,6 +45,15 @@ def xyz(text):
     if len(parts) != 3:
         raise argparse.ArgumentTypeError("three comma-separated numbers, got %r" % text)
     return tuple(float(v) for v in parts)
+
+
+def numbers(count, kind):
+    def parse(text):
+        parts = text.split(",")
+        if len(parts) != count:
+            raise argparse.ArgumentTypeError("%d comma-separated numbers, got %r" % (count, text))
+        return tuple(kind(v) for v in parts)
+    return parse
 
 
 def main():
@@ -73,6 +86,10 @@ def main():
     ap.add_argument("--anchor", action="store_true", help="add one anchor-codec row per row, matched to the model row's bytes")
     ap.add_argument("--anchor-qstep", type=float, help="code the anchor rows at this step (1/255 units) instead of matching bytes")
     ap.add_argument("--anchor-span", type=int, default=24, help="levels between quality 1 and quality 0 (raht.quality_levels)")
+    ap.add_argument("--screen-box", type=numbers(4, int), metavar="R0,R1,C0,C1", help="add the screen row: full quality inside this box of the judged view")
+    ap.add_argument("--screen-mask", metavar="FILE.png", help="add the screen row: quality from this 8-bit PNG of the judged view's size")
+    ap.add_argument("--gaze", type=numbers(4, float), metavar="ROW,COL,RADIUS,FALLOFF", help="add the screen row: quality around a gaze point")
+    ap.add_argument("--screen-tolerance", type=int, default=2, help="voxels behind the front a sampled pixel may lie (-1: own pixels only)")
     ap.add_argument("--repeat", type=int, default=0, help="time render_view and view_metrics over N further calls")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
@@ -114,15 +131,28 @@ def main():
         anchor = {"span": a.anchor_span}
         if a.anchor_qstep is not None:
             anchor.update(match=False, qstep=a.anchor_qstep / 255.0)
+    screen = None
+    if sum(v is not None for v in (a.screen_box, a.screen_mask, a.gaze)) > 1:
+        ap.error("--screen-box, --screen-mask and --gaze exclude each other")
+    if a.screen_box is not None:
+        screen = {"box": a.screen_box}
+    elif a.screen_mask is not None:
+        mask = io.read_png(a.screen_mask)
+        screen = {"image": mask if mask.ndim == 2 else mask[:, :, 0]}
+    elif a.gaze is not None:
+        screen = {"gaze": a.gaze}
+    if screen is not None:
+        screen["tolerance"] = None if a.screen_tolerance < 0 else a.screen_tolerance
     t0 = time.time()
     rows = evaluate_view_dependent(a.experiment, model, data, a.q_a, a.q_g, dev, a.out, view=view if a.mvub else a.view, H=a.height,
                                    W=a.width, gradient=gradient, roi=roi, save_images=True, details=details, facing=facing,
-                                   visibility=visibility, camera=camera, anchor=anchor)
+                                   visibility=visibility, camera=camera, anchor=anchor, screen=screen)
     t_all = time.time() - t0
     anchor_rows = {k: r for k, r in rows.items() if k.startswith("anchor_")}
     path = os.path.join(a.out, a.experiment, "view_dep.csv")
     with open(path, "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=["bpp", "q_a", "q_g", "key", "psnr", "ssim"] + (["codec", "qstep"] if a.anchor else []),
+        w = csv.DictWriter(f, fieldnames=["bpp", "q_a", "q_g", "key", "psnr", "ssim"] + (["codec", "qstep"] if a.anchor else [])
+                           + (["psnr_roi", "ssim_roi"] if screen is not None else []),
                            extrasaction="ignore")
         w.writeheader()
         for row in rows.values():
@@ -135,8 +165,8 @@ def main():
         q = camera.quantised()
         result["camera"] = {"position": list(a.camera), "look_at": list(look_at), "fov_y": a.fov, "pos_q": list(q.pos_q),
                             "axes_q": [list(r) for r in q.axes_q], "focal_q": q.focal_q, "near_q": q.near_q}
-    if a.facing or a.visibility:
-        result["t_%s_rows_s" % {4: "four", 5: "five"}[len(rows) - len(anchor_rows)]] = result.pop("t_three_rows_s")
+    if a.facing or a.visibility or screen is not None:
+        result["t_%s_rows_s" % {4: "four", 5: "five", 6: "six"}[len(rows) - len(anchor_rows)]] = result.pop("t_three_rows_s")
     if a.anchor:
         result["t_with_anchor_rows_s"] = result.pop(next(k for k in result if k.startswith("t_") and k.endswith("_rows_s")))
         result["anchor"] = {k: {"qstep_255": r["qstep"] * 255.0, "reached": r["reached"], "levels_bytes": r["levels_bytes"]}
@@ -146,6 +176,10 @@ def main():
         result["visibility"] = {"views": ["camera"] if camera is not None else (a.vis_views or [a.view]), "tolerance": a.vis_tolerance, "falloff": a.vis_falloff, "floor": a.vis_floor,
                                 "on_front": int((behind == 0).sum()), "within_tolerance": int((behind <= a.vis_tolerance).sum()),
                                 "offscreen": int((behind == render.OFFSCREEN).sum())}
+    if screen is not None:
+        _, count, _, score = details["screen"]
+        result["screen"] = {k: (list(v) if isinstance(v, tuple) else v) for k, v in screen.items() if k != "image"}
+        result["screen"].update(sampled=int((count > 0).sum()), full=int((score >= 1.0).sum()), mean_score=float(score.mean()))
     if a.repeat > 0:
         src, ref_img = details["source"]
         rec, img = details["uniform"]
