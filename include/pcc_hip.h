@@ -185,6 +185,58 @@ int pcc_voxelize(const float* xyz, const int32_t* batch, int64_t n, int32_t nbat
                  int32_t* vals, int64_t cap, int32_t* scratch, int32_t* out_coords, int32_t* out_first,
                  int32_t* out_npts, int64_t* out_sum, int32_t* out_row, int64_t* out_count, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Position scaling: lossy geometry by a rational scale, with the colours moved onto the quantised geometry
+ * ("recolouring") — what a conventional coder does at positionQuantizationScale < 1 (the reference's G-PCC
+ * operating points, plot.py:34 and evaluate_view_dep.py:95: scales 0.125, 0.25, 0.5, 0.75).
+ *   Scale.  s = num / den with integers 1 <= num <= den <= 255.  Per axis, in integers, with FLOOR division
+ *           (also for negative coordinates):
+ *               cell(p) = floor((2 p num + den) / (2 den))      p s rounded to nearest, halves up
+ *               pos(c)  = floor((2 c den + num) / (2 num))      c / s rounded to nearest, halves up
+ *           pos is strictly increasing (cells are at least one voxel apart), so distinct cells have distinct
+ *           positions and the lexicographic order of positions is that of cells; cell(pos(c)) = c.
+ *   Range.  A source coordinate beyond PCC_COORD_LIMIT, or a position that would fall beyond it, is an error
+ *           the caller raises on the host from the cloud's extent before a kernel runs (pos is monotone: the
+ *           extremes decide).  On the device a point with a coordinate beyond the limit, a batch index beyond
+ *           PCC_BATCH_LIMIT or an attribute that is not finite or has |a| > 1 makes pcc_scaled_cells report
+ *           *out_count = PCC_COUNT_ERR_RANGE (the outputs are then unspecified), as in pcc_voxelize.
+ *           num / den outside the range above, c outside 0 .. 16, a capacity that is no power of two or below
+ *           2 n, and null pointers are PCC_ERR_ARG, raised on the host before any launch.  n = 0 is valid.
+ *
+ * pcc_scaled_cells: coords int32 [n,4] (batch, x, y, z), attr float32 [n,c] or NULL when c = 0.  Outputs as
+ *   pcc_voxelize gives them: out_coords [n,4] = the distinct (batch, cell) in order of first appearance
+ *   (*out_count rows), out_first, out_npts, out_row, and out_sum int64 [n,c] = the exact Q32 sums of each
+ *   cell's OWN points (q = llrint((double)a * 4294967296.0)); on return (keys, vals, cap) is the hash table
+ *   of the cell set with tensor stride 1.  scratch: int32 [pcc_scan_scratch_elems(n)].  Eight launches.
+ *
+ * pcc_scaled_transfer: the same points and attributes, the table of their cell set (m rows), num, den.
+ *   Per point: out_nearest[i] = the cell row whose position pos(cell) is nearest to the point, out_d2[i]
+ *   (int64) = the squared distance in original voxels.  Per cell row: out_npts[r] = how many points chose
+ *   it, out_sum[r, ch] = the Q32 sum of their attributes; the call clears rows 0 .. m-1 of both first.
+ *   Ties.   Equidistant candidates resolve to the smallest (x, y, z), the rule of pcc_nn_search.  A cell of
+ *           another batch item is never a candidate.
+ *   Walk.   One thread per point walks shells k = 0, 1, 2 ... of Chebyshev radius k in the CELL domain
+ *           around cell(p) and measures true distances to pos(c).  Every cell of shell k differs from
+ *           cell(p) by exactly k along some axis a, and pos is monotone with pos(cell(p) - 1) < p <
+ *           pos(cell(p) + 1), so its distance^2 is at least
+ *               L(k) = min over a of min((pos(c0_a + k) - p_a)^2, (p_a - pos(c0_a - k))^2),
+ *           which does not decrease with k.  The walk stops before shell k once best < L(k); at best == L(k)
+ *           a tie may still be in shell k, so it is scanned.  Shell 0 holds the point's own cell, which is
+ *           in the set: the walk always ends, with no maximum radius and no retry on the host.  (A point
+ *           whose own cell is NOT in the table — a foreign table — or with a coordinate out of range gets
+ *           out_nearest = out_d2 = -1 and adds nothing.)
+ *   Sums.   Integer atomics only, behind the in-wave fold of equal rows the voxelisation uses: the outputs
+ *           are bitwise reproducible under any schedule.  The attributes are not range-checked again.
+ *   Two launches (clear, walk).
+ * ------------------------------------------------------------------------------------- */
+int pcc_scaled_cells(const int32_t* coords, int64_t n, const float* attr, int32_t c, int32_t num, int32_t den,
+                     uint64_t* keys, int32_t* vals, int64_t cap, int32_t* scratch, int32_t* out_coords,
+                     int32_t* out_first, int32_t* out_npts, int64_t* out_sum, int32_t* out_row, int64_t* out_count,
+                     void* stream);
+int pcc_scaled_transfer(const int32_t* coords, int64_t n, const float* attr, int32_t c, int32_t num, int32_t den,
+                        const uint64_t* keys, const int32_t* vals, int64_t cap, int64_t m, int32_t* out_nearest,
+                        int64_t* out_d2, int32_t* out_npts, int64_t* out_sum, void* stream);
+
 /* Kernel map (ME kernel_map, cached per coordinate manager): for every output row j and
  * kernel offset k, nbr[j*K + k] = input row at c_out + sign * off_k * step, or -1.
  * sign = +1 for (strided) convolution with step = input tensor stride; sign = -1 for

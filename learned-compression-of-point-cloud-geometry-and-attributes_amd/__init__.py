@@ -23,7 +23,7 @@ from .model import ColorModel  # noqa: F401
 from .normals import estimate_normals  # noqa: F401
 from .voxelize import voxelize, downsample, Voxelized  # noqa: F401
 from .pcqm import pcqm_voxel  # noqa: F401
-from . import synthetic, utils, parallel, render, augment, raht, anchor, rate_control, pcqm  # noqa: F401
+from . import synthetic, utils, parallel, render, augment, raht, anchor, rate_control, pcqm, rescale  # noqa: F401
 
 __all__ = ["ColorModel", "SparseTensor", "CoordMap", "build", "lib", "estimate_normals", "voxelize", "downsample", "Voxelized",
            "pcqm_voxel"]

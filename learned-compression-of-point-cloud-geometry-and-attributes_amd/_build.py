@@ -30,6 +30,9 @@ NO_SCRATCH = {
     # (scratch) copy of a point's channels would sit in front of every atomic of the accumulation pass
     "voxelize": ("first_rows_clear_kernel", "first_rows_insert_kernel", "first_rows_flag_kernel", "first_rows_finalize_kernel",
                  "voxelize_accumulate_kernel"),
+    # the position scaling (csrc/rescale.hip): the cell set is the voxelisation's, and the lattice walk keeps a point, its cell and
+    # the running best in registers through up to 27 table probes per shell; a spill would sit inside that loop
+    "rescale": ("first_rows_insert_kernel", "first_rows_finalize_kernel", "scaled_accumulate_kernel", "scaled_transfer_kernel"),
     # RAHT (csrc/raht.hip): a step is two gathered float64 rows in, two out; a spill would sit between the gather and the store
     "raht": ("raht_plan_kernel", "raht_step_kernel", "raht_fold_kernel"),
     # the perceptual metric (csrc/pcqm.hip): 20 running sums per point live through up to 4,218 probes and gathers; a spilled

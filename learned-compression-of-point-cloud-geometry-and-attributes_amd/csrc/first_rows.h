@@ -1,6 +1,6 @@
 // First-row-wins coordinate sets: unique candidate rows in order of first appearance, the lowest candidate index wins.  The one
 // builder of the library: the coordinate manager's stride maps and generative child sets (coords.hip, unique_coords), the rotation
-// (augment.hip) and the voxelisation (voxelize.hip) all go through first_rows_build.
+// (augment.hip), the voxelisation (voxelize.hip) and the position scaling (rescale.hip) all go through first_rows_build.
 //
 // The scheme: claim the candidate's slot in the hashed-voxel table (table_claim, common.h), atomicMin the candidate index into the
 // slot's value, flag the winners, scan the flags, and let every winner write its output row and turn its slot's value into the row

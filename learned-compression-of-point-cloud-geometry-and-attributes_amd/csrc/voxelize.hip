@@ -8,16 +8,16 @@
 // The coordinate set is the first-row set of first_rows.h (seven launches); every winner also records its point and zeroes its
 // accumulators.  Then ONE accumulation pass over the points: row = vals[slot_of[i]], integer atomic adds into out_npts / out_sum.
 // Integer addition commutes, so the bytes do not depend on the schedule; there is no
-// float atomic anywhere.  Clouds arrive spatially coherent, and many adders on one destination serialise, so a wave first folds
-// every run of consecutive lanes with the same row into its first lane (a segmented shuffle reduction, skipped by a wave-uniform
-// branch when no two neighbouring lanes share a row) and only run heads issue atomics.  Eight launches.
+// float atomic anywhere.  The adds go through the in-wave fold of equal rows that row_fold.h describes (fold_accumulate), shared
+// with the position scaling (rescale.hip).  Eight launches.
 #include "common.h"
 #include "first_rows.h"
+#include "row_fold.h"
 
 namespace pcc {
 
 constexpr int VOX_BLOCK = 256;
-constexpr int VOX_MAX_CHANNELS = 16;
+constexpr int VOX_MAX_CHANNELS = FOLD_MAX_CHANNELS;
 
 struct Voxelizer {
     const float* xyz;         // [n, 3]
@@ -42,33 +42,9 @@ struct Voxelizer {
     // a point with a cell out of range, a batch index without an item or an attribute that is not finite or exceeds 1 in magnitude
     // raises the error word and takes no part in the set (slot_of = mask + 1)
     __device__ __forceinline__ bool ok(int64_t i, bool ok) const {
-        for (int ch = 0; ch < c; ++ch) ok = ok && (fabsf(attr[i * c + ch]) <= 1.0f);      // false for NaN
-        return ok;
+        return attributes_ok(attr, c, i, ok);
     }
 };
-
-// The winner also zeroes the accumulators of its row: the caller hands over uninitialised buffers, and only the rows in use are
-// touched.
-struct VoxelSink {
-    int c;
-    int32_t *out_first, *out_npts;
-    int64_t* out_sum;
-    __device__ __forceinline__ void operator()(int32_t row, int64_t i) const {
-        out_first[row] = (int32_t)i;
-        out_npts[row] = 0;
-        for (int ch = 0; ch < c; ++ch) out_sum[(int64_t)row * c + ch] = 0;
-    }
-};
-
-// sum of v over lanes [lane, end) of the wave, `end` = one past the last lane of this lane's run; every lane takes part
-__device__ __forceinline__ int64_t run_sum(int64_t v, int lane, int end) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t o = __shfl_down(v, d, 64);
-        if (lane + d < end) v += o;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(VOX_BLOCK) void voxelize_accumulate_kernel(int64_t n, const float* __restrict__ attr, int c,
                                                                         const int32_t* __restrict__ vals, uint32_t mask,
@@ -76,35 +52,13 @@ __global__ __launch_bounds__(VOX_BLOCK) void voxelize_accumulate_kernel(int64_t 
                                                                         int32_t* __restrict__ out_npts, int64_t* __restrict__ out_sum) {
     // (no early return: the lanes behind the last point of a ragged wave take part in the shuffles, as runs of their own)
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     int32_t row = -1;                                  // no point, or a rejected one: adds nothing
     if (i < n) {
         const uint32_t slot = (uint32_t)slot_of[i];
         if (slot <= mask) row = vals[slot];
         out_row[i] = row;
     }
-    const int32_t before = __shfl_up(row, 1, 64);
-    const bool head = lane == 0 || before != row || row < 0;
-    const uint64_t heads = __ballot(head);
-    if (heads == ~0ull) {                              // wave-uniform: no two neighbouring lanes share a row
-        if (row >= 0) {
-            atomicAdd(&out_npts[row], 1);
-            for (int ch = 0; ch < c; ++ch) {
-                const int64_t q = llrint((double)attr[i * c + ch] * 4294967296.0);
-                atomicAdd(reinterpret_cast<unsigned long long*>(&out_sum[(int64_t)row * c + ch]), (unsigned long long)q);
-            }
-        }
-        return;
-    }
-    const uint64_t above = lane == 63 ? 0ull : (heads >> (lane + 1));
-    const int end = above ? lane + 1 + __builtin_ctzll(above) : 64;      // the next head, or the end of the wave
-    const bool adds = head && row >= 0;
-    if (adds) atomicAdd(&out_npts[row], end - lane);
-    for (int ch = 0; ch < c; ++ch) {
-        const int64_t q = row >= 0 ? llrint((double)attr[i * c + ch] * 4294967296.0) : 0;
-        const int64_t s = run_sum(q, lane, end);
-        if (adds) atomicAdd(reinterpret_cast<unsigned long long*>(&out_sum[(int64_t)row * c + ch]), (unsigned long long)s);
-    }
+    fold_accumulate(row, i, attr, c, out_npts, out_sum);
 }
 
 }  // namespace pcc

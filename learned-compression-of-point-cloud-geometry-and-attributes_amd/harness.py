@@ -137,7 +137,7 @@ def _levels_bytes(stream):
 
 
 def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, colorspace="yuv", pcqm=False, contexts=False, quality=None,
-                    block_log2=3, span=24):
+                    block_log2=3, span=24, scale=None, transfer="nearest"):
     """one row of the sweep table for the octree + RAHT anchor codec (anchor.py) at quantisation step ``qstep``: the keys of
     ``evaluate_frame``'s row without the quality-map pair, plus ``qstep`` and ``codec``.  ``bpp`` counts the whole PCA1 stream;
     the geometry is lossless, so ``sym_p2p_psnr`` is inf and ``n_decoded`` equals ``n_source``.  ``downsample`` and
@@ -146,8 +146,20 @@ def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, color
 
     ``quality`` (a per-point map as ``anchor.compress`` takes it, with ``block_log2`` and ``span``): region-wise quantisation;
     with ``downsample`` the map follows each voxel's first point.  The row gains ``levels_bytes``, what the stream spends on
-    the block levels (0 without a map)."""
-    from . import anchor
+    the block levels (0 without a map).
+
+    ``scale`` (what ``rescale.as_scale`` takes; not together with ``downsample``): lossy geometry by position scaling, the PCA2
+    stream (anchor.compress's ``scale`` and ``transfer``).  The decoded cloud lives on the ORIGINAL grid, so the metrics are
+    ``PointCloudMetric(original, decoded, resolution)`` at the resolution given and ``bpp`` is bits per original point: the row
+    stands on the axes of the model's rows.  ``n_decoded`` is the number of cells, ``sym_p2p_psnr`` is finite, and the row gains
+    ``scale`` (a float), ``scale_num``, ``scale_den`` and ``transfer``."""
+    from . import anchor, rescale
+    if scale is not None:
+        if downsample is not None:
+            raise ValueError("evaluate_anchor: scale and downsample are two ways to the same end; give one")
+        num, den = rescale.as_scale(scale)
+        if transfer not in rescale.TRANSFERS:
+            raise ValueError(f"transfer {transfer!r}: 'nearest' or 'cell'")
     n_input = None
     if downsample is not None:
         if not float(downsample) >= 1.0:
@@ -163,7 +175,8 @@ def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, color
 
     torch.cuda.synchronize()
     t0 = time.time()
-    stream = anchor.compress(src, qstep, colorspace=colorspace, contexts=contexts, quality=quality, block_log2=block_log2, span=span)
+    extra = {} if scale is None else {"scale": (num, den), "transfer": transfer}
+    stream = anchor.compress(src, qstep, colorspace=colorspace, contexts=contexts, quality=quality, block_log2=block_log2, span=span, **extra)
     torch.cuda.synchronize()
     t_c = time.time() - t0
 
@@ -183,6 +196,8 @@ def evaluate_anchor(data, qstep, device, resolution=1023, downsample=None, color
         row.update(_pcqm_columns(metric))
     if downsample is not None:
         row["downsample"], row["n_input"] = float(downsample), n_input
+    if scale is not None:
+        row.update(scale=num / den, scale_num=num, scale_den=den, transfer=transfer)
     return row
 
 
